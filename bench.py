@@ -6,6 +6,8 @@
     python bench.py --workload c2x22     # 22 chromosomes of C2's size as ONE block of 22 pieces
     python bench.py --gpus N             # N > 1: configs[3] (C4) over N GPUs; starts its own ranks (a child
                                          # torch.distributed.run on 127.0.0.1) and relays rank 0's line
+    python bench.py --full               # + CPU baseline, product entry point, stream-read probe, live counters
+    python bench.py --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W     # the same job under the driver's launcher
 
@@ -33,10 +35,21 @@ memory (+ the gather).  Rank 0 prints one JSON line.
 
 `roofline` prices the dominant kernel (site_counts) with HIP events on the launch stream:
 algorithmic bytes = resident sites x (n_ref + n_tgt + n_src) genotype bytes per launch of rank 0.
-`cpu_baseline` times the numpy oracle (the reference's per-window structure) on the host cores over
-a bounded site prefix of the same chromosome, before the GPU is initialised.  `score_path` is the
-rate of the product entry point on the same resident block: FeaturePreprocessor.score_windows (the
-same fused pass and windows stage) + the native TSV / log writer, next to the item-dictionary route.
+
+A plain run sets up, warms up, times the K steps and prints the line; everything that takes runs of
+its own is measured only with `--full`:
+  `cpu_baseline`   the numpy oracle (the reference's per-window structure) on the host cores over a
+                   bounded site prefix of the same chromosome, before the GPU is initialised
+  `score_path`     the rate of the product entry point on the same resident block:
+                   FeaturePreprocessor.score_windows (the same fused pass and windows stage) + the
+                   native TSV / log writer, next to the item-dictionary route
+  `roofline.stream_read_probe_gbps`  a plain streaming read of the resident block (the box's ceiling)
+  `roofline.traffic` measured live  two child runs under rocprofv3 --pmc (without --full: the stored figure)
+
+`--dump-outputs DIR` writes what the last timed step computed -- the records, offsets and candidate
+lists a caller of the resident path receives -- as DIR/<name>.npy (float64, finite: a window's undefined
+Q is written as 0 and flagged in records_q_defined), for output-for-output comparisons of two builds on
+the same seeded inputs.
 """
 
 from __future__ import annotations
@@ -61,6 +74,7 @@ SEED0 = 20260630  # + config number
 METRIC = "windows/sec (whole node) + achieved HBM GB/s, 50kb windows over 1e7 sites"
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 UQ = dict(w=0.01, x=0.5, quantile=0.95, y_list=[("=", 1.0)], anc=True)
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much; a larger output is sampled (seeded)
 
 
 def make_workload(name: str, sites=None, chroms=None, scaling: str = "strong", world: int = 1):
@@ -447,7 +461,8 @@ def measure_traffic(argv: list, kernel: str, timeout_s: float = 90.0):
     if prof is None:
         return None, "rocprofv3 not found"
     keep = [a for a in argv if a not in ("--traffic",)]
-    child = [sys.executable, str(Path(__file__).resolve()), *_without(keep, {"--steps": 1, "--warmup": 1, "--cpu-sites": 1, "--score-path": 1, "--traffic": 1}),
+    child = [sys.executable, str(Path(__file__).resolve()),
+             *_without(keep, {"--steps": 1, "--warmup": 1, "--cpu-sites": 1, "--score-path": 1, "--traffic": 1, "--full": 0, "--dump-outputs": 1}),
              "--steps", "3", "--warmup", "1", "--cpu-sites", "0", "--score-path", "off", "--traffic", "off"]  # fmt: skip
     got = {}
     with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
@@ -499,6 +514,39 @@ def _without(argv: list, flags: dict) -> list:
             continue
         out.append(a)
     return out
+
+
+def dump_outputs(res, out_dir: str) -> dict:
+    """What the last timed step computed, as a caller of the resident path receives it (WindowResults: the
+    24-byte records field by field, the list offsets, both candidate lists), written as ``out_dir/<name>.npy``
+    in float64 (every integer here is far below 2**53, so the cast is exact).  Q is NaN for a window without
+    candidates; the files hold finite numbers only, so ``records_q`` carries 0 there and ``records_q_defined``
+    (1 where Q is a number, 0 where it is NaN) says which.  Above DUMP_BYTES in all, each array is cut to the
+    same share of its elements by a fixed-seed sample -- arrays of one length (the record fields, the mask) by
+    the same indices -- so equal jobs dump equal files.  Returns {name: shape written}."""
+    arrays = {f"records_{f}": res.records[f] for f in res.records.dtype.names}
+    arrays.update(offsets=res.offsets, cdd_u=res.cdd_u, cdd_q=res.cdd_q)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    defined = ~np.isnan(arrays["records_q"])
+    arrays["records_q"] = np.where(defined, arrays["records_q"], 0.0)
+    arrays["records_q_defined"] = defined.astype(np.float64)
+    bad = [k for k, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise ValueError(f"non-finite values in the outputs {bad}")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        picks = {}  # flat length -> sorted sample indices (one draw per length)
+        for k, a in arrays.items():
+            n = a.size
+            if n not in picks:
+                keep = int(n * DUMP_BYTES // total)
+                picks[n] = np.sort(np.random.default_rng([SEED0, n]).choice(n, keep, replace=False))
+            arrays[k] = a.reshape(-1)[picks[n]]
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(out / f"{k}.npy", a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def source_digest() -> str:
@@ -618,6 +666,34 @@ def _trim(pop, n_sites):
     return TiledPop(pop.tiles, n_sites, pop.n_ind)
 
 
+def library_is_current() -> bool:
+    """True when ``build()`` would compile and link nothing: every object is newer than its source and the
+    headers, and libsaihip.so newer than every object (the rules of sai_amd/_build.py).  Read-only: the
+    benchmark may run as a user who can read the built tree but not write to it."""
+    from sai_amd import _build
+
+    def newer(target: Path, sources) -> bool:
+        return target.exists() and all(Path(s).stat().st_mtime <= target.stat().st_mtime for s in sources)
+
+    headers = [_build.INCLUDE / "saihip.h", *sorted(_build.CSRC.glob("*.hpp"))]
+    objs = [_build.OBJ / (Path(u).stem + ".o") for u in _build.UNITS]
+    return all(newer(o, [_build.CSRC / u, *headers]) for o, u in zip(objs, _build.UNITS)) and newer(_build.LIB, objs)
+
+
+def ensure_library() -> None:
+    """Build what is stale (``__graft_entry__.build``, which takes a lock file in the library directory); a
+    current tree is only imported and its library loaded, so nothing is written."""
+    if not library_is_current():
+        import __graft_entry__ as entry
+
+        entry.build()
+        return
+    import sai_amd.stats  # noqa: F401
+    from sai_amd import _ffi
+
+    _ffi.load()  # every symbol of include/saihip.h resolves
+
+
 def self_launch(n_ranks: int, argv: list, result_out, script: str = "") -> int:
     """`python bench.py --gpus N` without a launcher around it: build the library once, then run the N
     ranks as ONE child process tree (`python -m torch.distributed.run ... bench.py <same arguments>`,
@@ -628,7 +704,8 @@ def self_launch(n_ranks: int, argv: list, result_out, script: str = "") -> int:
     same way from the parent that owns the task list (mp_pool.py:45-73)."""
     from sai_amd.launcher import launch_ranks
 
-    return launch_ranks(n_ranks, argv, script=script or str(Path(__file__).resolve()), stdout=result_out, who="bench.py")
+    ensure_library()  # once, before N ranks would each check the tree
+    return launch_ranks(n_ranks, argv, script=script or str(Path(__file__).resolve()), stdout=result_out, build=False, who="bench.py")
 
 
 class HipDevice:
@@ -758,19 +835,30 @@ def main(argv=None, device=None) -> None:
     ap.add_argument("--anc", choices=["true", "false"], default="true",
                     help="anc_allele_available of every parameter set: true = the headline; false = SURVEY 8(d)'s "
                     "second row (sources also matched against 1 - y, matching sites inverted; stat_utils.py:146-160)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline, the product entry point (score_path), "
+                    "the stream-read probe and the live HBM counters (--traffic); a plain run only sets up, warms up, "
+                    "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (records, offsets, candidate lists) "
+                    "as DIR/<name>.npy in float64 (records_q_defined flags the windows whose Q is undefined)")
     ap.add_argument("--traffic", choices=["auto", "live", "static", "off"], default="auto",
                     help="roofline.traffic: live = two short child runs of this command under rocprofv3 --pmc (FETCH_SIZE, "
-                    "WRITE_SIZE) after the timed region (each ended after 90 s at the latest); static = the figure kept in "
-                    "profiles/traffic.json (N > 1: rank 0's share of it); auto = live on one GPU for a full-size workload "
-                    "when rocprofv3 is there, else static")
-    ap.add_argument("--cpu-runs", type=int, default=3, help="timed runs of the CPU baseline (the median is reported)")
-    ap.add_argument("--cpu-run-seconds", type=float, default=5.0, help="minimum length of one CPU run (whole passes)")
-    ap.add_argument("--cpu-sites", type=float, default=1e6, help="site prefix timed on the CPU (0 = skip)")
+                    "WRITE_SIZE) after the timed region (each ended after 90 s at the latest; --full only); static = the "
+                    "figure kept in profiles/traffic.json (N > 1: rank 0's share of it); auto = live with --full on one GPU "
+                    "for a full-size workload when rocprofv3 is there, else static")
+    ap.add_argument("--cpu-runs", type=int, default=3, help="timed runs of the CPU baseline (the median is reported; --full only)")
+    ap.add_argument("--cpu-run-seconds", type=float, default=5.0, help="minimum length of one CPU run (whole passes; --full only)")
+    ap.add_argument("--cpu-sites", type=float, default=1e6, help="site prefix timed on the CPU (0 = skip; --full only)")
     ap.add_argument("--cpu-workers", type=int, default=0, help="0 = usable cores (affinity mask capped by the cgroup quota)")
     ap.add_argument("--score-path", choices=["auto", "on", "off"], default="auto",
-                    help="also time the product entry point (run_windows + items + text) on the resident block "
+                    help="with --full, also time the product entry point (run_windows + items + text) on the resident block "
                     "(auto = on for one GPU and a one-chromosome workload)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process only builds and starts the ranks
@@ -784,9 +872,7 @@ def main(argv=None, device=None) -> None:
 
     # build first, before anything touches the GPU or joins a process group: hipcc children are
     # forked from a process that has not initialised HIP; concurrent ranks serialise on a file lock
-    import __graft_entry__ as entry
-
-    entry.build()
+    ensure_library()
 
     name = args.workload if args.workload != "auto" else ("c3" if world == 1 else "c4")
     wl = make_workload(name, args.sites, args.chroms, args.scaling, world)
@@ -801,7 +887,7 @@ def main(argv=None, device=None) -> None:
         wl.description += "; anc_allele_available=False (mirror match + inversion)"
 
     cpu = None
-    if rank == 0 and args.cpu_sites > 0:
+    if args.full and rank == 0 and args.cpu_sites > 0:
         # a one-GPU box grants a 16-CPU share of the host whatever nproc says.  In an N > 1 job rank 0 times the
         # baseline HERE, before it joins the process group: the other ranks wait for it in init_process_group
         # (timeout 10 minutes; the baseline takes about half a minute) and their cores are idle meanwhile
@@ -933,17 +1019,18 @@ def main(argv=None, device=None) -> None:
         res = scorer.results()  # also checks the candidate buffers were large enough
 
     if rank == 0:
+        dumped = dump_outputs(res, args.dump_outputs) if args.dump_outputs else None
         kernel_ms = device.site_pass_ms(scorer)
         avg_ms = sum(kernel_ms) / len(kernel_ms)
         alg_bytes = device.genotype_bytes(block, args.layout)
         achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
-        stream_read = device.stream_read_probe(block)
+        stream_read = device.stream_read_probe(block) if args.full else None
         n_sites_rank0 = block.n_real_sites
         path_bytes = alg_bytes + 4 * n_sites_rank0 + 24 * n_sets * scorer.n_windows
         traffic, traffic_source = static_traffic(wl, args, world, n_sites_rank0)
         score_path = None
         want_sp = args.score_path == "on" or (args.score_path == "auto" and world == 1)
-        if want_sp and world == 1 and len(wl.chroms) == 1 and args.layout == "int8":
+        if args.full and want_sp and world == 1 and len(wl.chroms) == 1 and args.layout == "int8":
             try:
                 score_path = device.score_path(wl, block, lay)
             except Exception as exc:  # noqa: BLE001 - a secondary figure must not cost the headline line
@@ -1017,8 +1104,8 @@ def main(argv=None, device=None) -> None:
                 "launch_ms_min_median_max": [round(v, 4) for v in (min(site_ms), sorted(site_ms)[len(site_ms) // 2], max(site_ms))] if site_ms else None,
                 "launches_over_1p1_median": int(sum(1 for v in site_ms if v > 1.1 * sorted(site_ms)[len(site_ms) // 2])) if site_ms else None,
                 "rank": 0,
-                "stream_read_probe_gbps": round(stream_read, 1),
-                "frac_of_stream_read_probe": round(achieved / stream_read, 4),
+                "stream_read_probe_gbps": round(stream_read, 1) if stream_read is not None else None,
+                "frac_of_stream_read_probe": round(achieved / stream_read, 4) if stream_read is not None else None,
                 # genotypes + 4 B per position + 24 B per record, over the whole step
                 "whole_path_bytes_per_step": path_bytes,
                 "whole_path_gbps_this_rank": round(path_bytes / (dt / args.steps) / 1e9, 1),
@@ -1027,14 +1114,17 @@ def main(argv=None, device=None) -> None:
             # the product entry point on the same block (score_path.value): what a caller of `score` gets per second
             "product_windows_per_s": score_path.get("value") if isinstance(score_path, dict) else None,
             "score_path": score_path,
+            "full": bool(args.full),
+            "outputs": {"dir": args.dump_outputs, "arrays": dumped} if dumped is not None else None,
         }
         reduced = bool(args.sites or args.chroms or args.missing_per_million)
         # never under a profiler: its preloaded library has initialised the GPU in every process of the tree, and a
         # nested rocprofv3 would exec its target from such a process (refused on this pool, for good reason)
         profiled = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
-        if profiled and args.traffic in ("auto", "live"):
+        # the live counters take two runs of their own: --full only
+        if args.full and profiled and args.traffic in ("auto", "live"):
             line["roofline"]["traffic_source"] = f"{traffic_source or 'none stored'}; not measured live: this run is itself under a profiler"
-        elif device.name == "hip" and world == 1 and not dist_on and (args.traffic == "live" or (args.traffic == "auto" and not reduced)):
+        elif args.full and device.name == "hip" and world == 1 and not dist_on and (args.traffic == "live" or (args.traffic == "auto" and not reduced)):
             # the counters need their own runs (the profiler changes the clock): release this process's HBM first
             kernel = line["roofline"]["kernel"]
             del scorer, block, res

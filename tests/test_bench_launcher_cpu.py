@@ -11,6 +11,8 @@ import subprocess
 import sys
 import textwrap
 
+import pytest
+
 from conftest import ROOT
 
 RANK_SCRIPT = textwrap.dedent(
@@ -159,3 +161,27 @@ def test_live_traffic_reads_the_counters_of_two_child_runs(tmp_path, monkeypatch
             assert stat[2] == "Z", (pid, stat[2])  # at most a zombie waiting for init
         except FileNotFoundError:
             pass
+
+
+def test_a_built_tree_is_loaded_without_writing_to_it(tmp_path, monkeypatch):
+    """The benchmark may run as a user who can read the built tree but not write to it: on a current tree it
+    loads the library without calling build() (which takes a lock file in the library directory); a tree
+    whose objects are missing is stale and is built."""
+    import __graft_entry__ as entry
+    import bench
+    from sai_amd import _build
+
+    entry.build()
+    assert bench.library_is_current()
+    lib_dir = sorted(p.name for p in _build.LIB.parent.iterdir())
+
+    def refuse(*a, **k):
+        raise AssertionError("build() called")
+
+    monkeypatch.setattr(entry, "build", refuse)
+    bench.ensure_library()
+    assert sorted(p.name for p in _build.LIB.parent.iterdir()) == lib_dir
+    monkeypatch.setattr(_build, "OBJ", tmp_path / "obj")
+    assert not bench.library_is_current()
+    with pytest.raises(AssertionError, match=r"build\(\) called"):
+        bench.ensure_library()

@@ -354,7 +354,7 @@ def test_the_two_rank_line_is_complete(tmp_path):
 
     import torch.multiprocessing as mp
 
-    argv = ["--gpus", "2", "--workload", "c4", "--sites", "2600", "--chroms", "5", "--steps", "2", "--warmup", "1",
+    argv = ["--gpus", "2", "--workload", "c4", "--sites", "2600", "--chroms", "5", "--steps", "2", "--warmup", "1", "--full",
             "--cpu-sites", "2600", "--cpu-runs", "2", "--cpu-run-seconds", "0.2", "--cpu-workers", "2"]  # fmt: skip
     mp.spawn(_bench_main_worker, args=(2, _free_port(), str(tmp_path), argv), nprocs=2, join=True)
     assert (tmp_path / "stdout1.txt").read_text() == ""
@@ -385,6 +385,69 @@ def test_the_two_rank_line_is_complete(tmp_path):
     cb = line["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] == 2 and cb["value"] > 0 and "before it joined the process group" in cb["sample"]
     assert cfg["u_sum"] > 0 and cfg["q_finite"] > 0
+
+
+def test_plain_line_is_lean_and_dumps_what_rank_0_received(tmp_path):
+    """Without --full no CPU baseline is timed (whatever --cpu-sites says) and the stream-read probe is not run;
+    --dump-outputs writes, on rank 0 only, what the last step computed: the two-rank job dumps the very arrays of
+    the one-rank job."""
+    import json
+
+    import torch.multiprocessing as mp
+
+    argv = ["--workload", "c4", "--sites", "2600", "--chroms", "3", "--steps", "2", "--warmup", "1", "--cpu-sites", "2600"]
+    lines = {}
+    for world in (1, 2):
+        out = tmp_path / f"w{world}"
+        out.mkdir()
+        mp.spawn(_bench_main_worker, args=(world, _free_port(), str(out), ["--gpus", str(world), *argv, "--dump-outputs", str(out / "npy")]),
+                 nprocs=world, join=True)  # fmt: skip
+        (text,) = [ln for ln in (out / "stdout0.txt").read_text().splitlines() if ln.startswith("{")]
+        lines[world] = json.loads(text)
+    one, two = lines[1], lines[2]
+    for line in (one, two):
+        assert line["full"] is False and line["cpu_baseline"] is None and line["score_path"] is None
+        assert line["roofline"]["stream_read_probe_gbps"] is None and line["steps"] == 2 and line["ms_per_step"] > 0
+    names = sorted(one["outputs"]["arrays"])
+    assert names == sorted(two["outputs"]["arrays"]) and len(names) == 9 and "records_q_defined" in names
+    for k in names:
+        a, b = np.load(tmp_path / "w1" / "npy" / f"{k}.npy"), np.load(tmp_path / "w2" / "npy" / f"{k}.npy")
+        assert a.dtype == np.float64 and np.isfinite(a).all() and a.tobytes() == b.tobytes(), k
+    assert np.load(tmp_path / "w1" / "npy" / "records_q_defined.npy").sum() == one["config"]["q_finite"]
+    assert np.load(tmp_path / "w1" / "npy" / "records_u_count.npy").sum() == one["config"]["u_sum"] > 0
+    assert np.load(tmp_path / "w1" / "npy" / "cdd_u.npy").size == one["config"]["cdd_u_entries"]
+
+
+def test_dump_outputs_samples_a_large_output_the_same_way(tmp_path, monkeypatch):
+    """Q's NaN (a window without candidates) is written as 0 next to a mask, so every file is finite; above the size
+    limit every array is cut to the same share by a fixed-seed sample, the record fields and the mask at the same
+    indices: equal inputs, equal files."""
+    import bench
+    from sai_amd.engine import RECORD_DTYPE, WindowResults
+
+    rng = np.random.default_rng(3)
+    rec = np.zeros((2, 500), dtype=RECORD_DTYPE)
+    rec["u_count"] = np.arange(rec.size).reshape(rec.shape)  # the element's own index: shows which ones a sample kept
+    rec["q"] = rng.random(rec.shape)
+    rec["q"][rng.random(rec.shape) < 0.3] = np.nan
+    res = WindowResults(rec, rng.integers(0, 1 << 40, (2, 500, 2)), rng.integers(0, 1 << 30, 4000).astype(np.int32),
+                        rng.integers(0, 1 << 30, 3000).astype(np.int32))  # fmt: skip
+    whole = bench.dump_outputs(res, str(tmp_path / "whole"))
+    assert whole["cdd_u"] == [4000] and whole["records_q"] == [2, 500]
+    assert np.array_equal(np.load(tmp_path / "whole" / "offsets.npy"), res.offsets.astype(np.float64))
+    q, q_defined = np.load(tmp_path / "whole" / "records_q.npy"), np.load(tmp_path / "whole" / "records_q_defined.npy")
+    assert np.array_equal(q_defined, (~np.isnan(rec["q"])).astype(np.float64)) and 0 < q_defined.sum() < rec.size
+    assert np.array_equal(q, np.nan_to_num(rec["q"], nan=0.0))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40_000)
+    a, b = bench.dump_outputs(res, str(tmp_path / "a")), bench.dump_outputs(res, str(tmp_path / "b"))
+    assert a == b and sum(8 * np.prod(s) for s in a.values()) <= 40_000
+    for k in a:
+        x = np.load(tmp_path / "a" / f"{k}.npy")
+        assert x.tobytes() == np.load(tmp_path / "b" / f"{k}.npy").tobytes() and x.size > 0
+        assert np.isfinite(x).all() and np.isin(x, np.load(tmp_path / "whole" / f"{k}.npy")).all()
+    kept = np.load(tmp_path / "a" / "records_u_count.npy").astype(np.int64)  # the flat indices the record sample kept
+    assert kept.size < rec.size and np.array_equal(np.load(tmp_path / "a" / "records_q.npy"), q.reshape(-1)[kept])
+    assert np.array_equal(np.load(tmp_path / "a" / "records_q_defined.npy"), q_defined.reshape(-1)[kept])
 
 
 def test_three_ranks_report_where_they_ran(tmp_path):

@@ -35,7 +35,7 @@ for f in sorted(SRC.glob("bench_*.json")):
     probes[name] = line["roofline"].get("stream_read_probe_gbps")
     base = name[: -len("_second_box")] if name.endswith("_second_box") else name  # (tools/evidence.sh second_box: another gpurun call, another box)
     flags = {"c3": "", "c3_noanc": " --anc false", "c3_packed2": " --layout packed2", "c4": " --workload c4 --steps 20 --cpu-sites 0"}.get(base, f" --workload {base}")
-    keep(f"r05_bench_{name}.json", json.dumps(line), probes[name], f"python bench.py{flags}")
+    keep(f"r05_bench_{name}.json", json.dumps(line), probes[name], f"python bench.py --full{flags}")
 box = probes.get("c3")
 for src, dst, cmd, head in (
     ("eval_cost.txt", "r05_eval_cost.txt", "python tools/eval_cost.py",
@@ -58,7 +58,7 @@ if (SRC / "rehearse_n2_on_one_gpu.json").exists() and (SRC / "rehearse_n2_on_one
     line = json.loads((SRC / "rehearse_n2_on_one_gpu.json").read_text().strip().splitlines()[-1])
     if line["config"]["source_digest"] == here:
         keep("r05_rehearse_n2_on_one_gpu.json", json.dumps(line), line["roofline"].get("stream_read_probe_gbps"),
-             "SAI_BENCH_DEVICE=0 SAI_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 1 --cpu-sites 0 (both ranks on the box's one GPU)")
+             "SAI_BENCH_DEVICE=0 SAI_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 1 --full --cpu-sites 0 (both ranks on the box's one GPU)")
 mfile.write_text(json.dumps(manifest, indent=1, sort_keys=True) + "\n")
 # counters of other trees are not this tree's traffic: dropped before this tree's are added
 tfile = DST / "traffic.json"

@@ -14,7 +14,7 @@ mkdir -p $OUT
 part=${1:-benches}
 bench() { # name, flags...
   name=$1; shift
-  python3 bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "bench $name failed"; tail -5 $OUT/bench_$name.err; return 1; }
+  python3 bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "bench $name failed"; tail -5 $OUT/bench_$name.err; return 1; }
   python3 -c "
 import json; d = json.loads(open('$OUT/bench_$name.json').read()); r = d['roofline']
 print('$name', 'value', d['value'], 'ms/step', d['ms_per_step'], 'site', r['avg_launch_ms'], 'frac', r['frac'], 'probe', r['stream_read_probe_gbps'], 'traffic', r['traffic'], 'product', d.get('product_windows_per_s'))"
@@ -39,7 +39,7 @@ second_box)  # the headline lines once more in another call: the pool's boxes di
 c4)
   bench c4 --workload c4 --steps 20 --cpu-sites 0
   bash tools/profile.sh r05_c4 c4
-  SAI_BENCH_DEVICE=0 SAI_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 5 --warmup 1 --cpu-sites 0 > $OUT/rehearse_n2_on_one_gpu.json 2> $OUT/rehearse_n2.err || tail -5 $OUT/rehearse_n2.err
+  SAI_BENCH_DEVICE=0 SAI_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 5 --warmup 1 --full --cpu-sites 0 > $OUT/rehearse_n2_on_one_gpu.json 2> $OUT/rehearse_n2.err || tail -5 $OUT/rehearse_n2.err
   ;;
 esac
 echo "evidence part $part done"

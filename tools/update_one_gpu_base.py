@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/one_gpu_base.json from a one-GPU bench line of the N > 1 job (`python bench.py --workload c4`):
+"""profiles/one_gpu_base.json from a one-GPU bench line of the N > 1 job (`python bench.py --full --workload c4`):
 the figure every `--gpus N` line names as its strong-scaling denominator, tied to the digest of the sources
 it was measured on (bench.source_digest) -- a line from another tree is handed out as `stale`, not as the base.
 Usage: python tools/update_one_gpu_base.py profiles/r04_bench_c4.json ["note about the box"]"""
@@ -18,7 +18,7 @@ rec = {
     "windows": line["config"]["windows_total"],
     "steps": line["steps"],
     "source_digest": line["config"]["source_digest"],
-    "source": f"{src.as_posix()} (python bench.py --workload c4 --steps {line['steps']}, one MI355X, {line['config']['windows_total']} windows, "
+    "source": f"{src.as_posix()} (python bench.py --full --workload c4 --steps {line['steps']}, one MI355X, {line['config']['windows_total']} windows, "
               f"{line['roofline']['algorithmic_bytes_per_launch'] / 1e9:.1f} GB resident)",
     "box": (sys.argv[2] if len(sys.argv) > 2 else "") + f" stream-read probe {line['roofline']['stream_read_probe_gbps']} GB/s in the same run",
 }
