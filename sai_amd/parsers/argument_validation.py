@@ -43,6 +43,19 @@ def existed_file(path: Optional[str]) -> Optional[str]:
     raise argparse.ArgumentTypeError(f"{path} is not found")
 
 
+def existed_fileset(prefix: Optional[str]) -> Optional[str]:
+    """The prefix itself (a trailing ``.bed`` is dropped) when PREFIX.bed, PREFIX.bim and PREFIX.fam are
+    regular files (or it is None)."""
+    if prefix is None:
+        return None
+    if prefix.endswith(".bed") and not os.path.isfile(prefix + ".bed"):
+        prefix = prefix[: -len(".bed")]
+    for ext in (".bed", ".bim", ".fam"):
+        if not os.path.isfile(prefix + ext):
+            raise argparse.ArgumentTypeError(f"{prefix}{ext} is not found")
+    return prefix
+
+
 def validate_stat_type(label: str) -> str:
     """A statistic label of the form letter + two digits: ``U05`` (U with x > 0.05), ``Q95`` (Q at the
     0.95 quantile).  Not used by the current commands; kept because the module's interface has it

@@ -7,7 +7,7 @@ import argparse
 
 from ..launcher import workers_from_env
 from ..sai import score
-from .argument_validation import existed_file, positive_int
+from .argument_validation import existed_file, existed_fileset, positive_int
 
 
 def resolve_workers(args: argparse.Namespace) -> int:
@@ -22,10 +22,20 @@ def resolve_workers(args: argparse.Namespace) -> int:
     return args.num_workers
 
 
+def resolve_input(args: argparse.Namespace) -> str:
+    """Exactly one of ``--vcf`` and ``--bfile``: the path ``score`` takes as its ``vcf_file`` (a fileset is handed
+    over as ``PREFIX.bed``).  Decided here, not by argparse's ``required=True`` -- neither flag is required alone --
+    but reported the same way, as a usage error with status 2."""
+    if (args.vcf is None) == (args.bfile is None):
+        args.score_parser.error("exactly one of the arguments --vcf and --bfile is required")
+    return args.vcf if args.bfile is None else args.bfile + ".bed"
+
+
 def _run_score(args: argparse.Namespace) -> None:
+    source = resolve_input(args)
     resolve_workers(args)
     score(
-        vcf_file=args.vcf,
+        vcf_file=source,
         chr_name=args.chr_name,
         win_len=args.win_len,
         win_step=args.win_step,
@@ -38,7 +48,12 @@ def _run_score(args: argparse.Namespace) -> None:
 
 def add_score_parser(subparsers) -> None:
     parser = subparsers.add_parser("score", help="Run the score command based on specified parameters.")
-    parser.add_argument("--vcf", type=existed_file, required=True, help="Path to the VCF file containing variant data.")
+    parser.add_argument("--vcf", type=existed_file, default=None, help="Path to the VCF file containing variant data.")
+    # not a flag of the reference: the same genotypes as a PLINK 1 binary fileset, decoded on the GPU
+    parser.add_argument("--bfile", type=existed_fileset, default=None, metavar="PREFIX",
+                        help="Prefix of a PLINK 1 binary fileset (PREFIX.bed + PREFIX.bim + PREFIX.fam, variant-major) to "
+                        "read instead of a VCF; A2 is taken as the reference allele and A1 as the alternative one. "
+                        "Exactly one of --vcf and --bfile is required.")  # fmt: skip
     parser.add_argument("--chr-name", dest="chr_name", type=str, required=True,
                         help="Chromosome name to analyze from the VCF file.")  # fmt: skip
     parser.add_argument("--win-len", dest="win_len", type=positive_int, default=50000,

@@ -1,0 +1,365 @@
+"""PLINK 1 binary filesets (PREFIX.bed + PREFIX.bim + PREFIX.fam) as an input of ``score``.
+
+A ``.bed`` holds a genotype in 2 bits -- 16 times fewer bytes than VCF text -- in rows of fixed length, so
+the rows of a region are byte ranges that follow from the ``.bim`` alone.  The host index
+(``sai_plink_open``, sai_amd/csrc/plink/plink_index.cpp) resolves the samples and selects the rows; the
+``.bed`` bytes cross PCIe as they are and ``sai_plink_decode`` turns them into the int8
+[record][sample] block ``sai_tokenize_gt`` writes for VCF text, so everything behind the readers is
+shared with the VCF route.  A2 plays REF and A1 plays ALT; the dosage table, and what is refused, are
+in DESIGN_INGEST.md ("PLINK 1 filesets").
+
+``load_dosage`` / ``load_dosage_device`` return what ``native_vcf.load_dosage`` /
+``device_vcf.load_dosage_device`` return.  Unlike a VCF pass, one pass serves a sample that is asked
+for more than once (a sample that sits in populations of different ploidy): every request is a slot.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import Optional, Sequence
+
+import numpy as np
+
+from .. import _ffi, _ffi_plink
+from .native_vcf import default_threads
+
+BUFFER_BYTES = 32 << 20  # as the VCF route (device_vcf.BUFFER_BYTES); SAI_AMD_INGEST_BUFFER overrides it
+_MAGIC = b"\x6c\x1b"
+_EXTENSIONS = (".bed", ".bim", ".fam")
+_READ_THROUGH_BYTES = 64 << 10  # unselected rows between two selected ones are read along up to this many bytes
+_PREAD_PIECE = 4 << 20  # a batch is read by several threads in pieces of this size
+
+
+def fileset_prefix(path) -> Optional[str]:
+    """PREFIX when ``path`` (``PREFIX.bed`` or the bare ``PREFIX``) names a PLINK 1 fileset: the three
+    files exist and the ``.bed`` starts with PLINK's magic bytes.  By content, never by the extension
+    alone -- ``.bed`` is also what ancestral-allele files are called."""
+    if path is None:
+        return None
+    text = os.fspath(path)
+    candidates = ([text[: -len(".bed")]] if text.endswith(".bed") else []) + [text]
+    for prefix in candidates:
+        if prefix and all(os.path.isfile(prefix + ext) for ext in _EXTENSIONS):
+            try:
+                with open(prefix + ".bed", "rb") as f:
+                    if f.read(2) == _MAGIC:
+                        return prefix
+            except OSError:
+                pass
+    return None
+
+
+def is_fileset(path) -> bool:
+    return fileset_prefix(path) is not None
+
+
+def _prefix_of(path) -> str:
+    """The prefix a reader hands to the library: the detected one, else the path as a prefix (the library
+    then says which file is missing or what is wrong with the ``.bed``)."""
+    found = fileset_prefix(path)
+    if found is not None:
+        return found
+    text = os.fspath(path)
+    return text[: -len(".bed")] if text.endswith(".bed") else text
+
+
+def _error(lib) -> ValueError:
+    return ValueError(lib.sai_last_error().decode("utf-8", "replace"))
+
+
+def scan_first_last(path, chr_name: str):
+    """First and last position of the first contiguous run of ``chr_name`` in the ``.bim`` (None, None if
+    absent): ``native_vcf.scan_first_last`` for a fileset."""
+    lib = _ffi_plink.load_host()
+    first, last = C.c_int64(-1), C.c_int64(-1)
+    if lib.sai_plink_scan(os.fsencode(_prefix_of(path)), str(chr_name).encode(), C.byref(first), C.byref(last)):
+        raise _error(lib)
+    return (None, None) if first.value < 0 else (int(first.value), int(last.value))
+
+
+class _Index:
+    """The host index of one region: positions, the ``.bed`` row and the flip flag of every selected row,
+    the ``.fam`` column of every slot."""
+
+    def __init__(self, lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads):
+        self.prefix = _prefix_of(path)
+        n = len(samples)
+        names = (C.c_char_p * n)(*[s.encode() for s in samples])
+        pl = (C.c_int32 * n)(*[int(p) for p in ploidies])
+        handle = C.c_void_p()
+        if lib.sai_plink_open(
+            os.fsencode(self.prefix), str(chr_name).encode(), -1 if start is None else int(start), -1 if end is None else int(end),
+            n, names, pl, os.fsencode(anc_allele_file) if anc_allele_file else None, n_threads or default_threads(), C.byref(handle),
+        ):  # fmt: skip
+            raise _error(lib)
+        try:
+            v = [C.c_int64() for _ in range(8)]
+            if lib.sai_plink_index_info(handle, *[C.byref(x) for x in v]):
+                raise _error(lib)
+            n_rows, self.n_matched, self.n_anc, self.row_bytes, self.n_fam, self.n_bim, self.first, self.last = (int(x.value) for x in v)
+            self.pos = np.empty(n_rows, dtype=np.int32)
+            self.file_row = np.empty(n_rows, dtype=np.int64)
+            self.flip = np.empty(n_rows, dtype=np.uint8)
+            self.col_of_slot = np.empty(n, dtype=np.int32)
+            if lib.sai_plink_index_copy(handle, *(a.ctypes.data_as(C.c_void_p) for a in (self.pos, self.file_row, self.flip, self.col_of_slot))):
+                raise _error(lib)
+        finally:
+            lib.sai_plink_index_close(handle)
+        self.samples = list(samples)
+        self.ploidies = np.asarray([int(p) for p in ploidies], dtype=np.int32)
+        self.n_rows, self.n_slots = n_rows, n
+        cols = self.col_of_slot
+        # the two promises that select the kernel's fast path
+        self.first_col = int(cols[0]) if n and np.array_equal(cols, np.arange(cols[0], cols[0] + n, dtype=np.int32)) else -1
+        self.uniform_ploidy = int(self.ploidies[0]) if n and bool((self.ploidies == self.ploidies[0]).all()) else 0
+
+    def batches(self, cap: int):
+        """Cut the selected rows into batches of at most ``cap`` bytes of whole rows.  Selected rows that are
+        close in the file are read as one range, the few rows between them included (a ``pread`` per row
+        would cost more than their bytes); the ranges of a batch lie back to back in its buffer.  Yields
+        ``(k0, k1, row_in_batch int32 [k1 - k0], n_batch_rows, reads)`` with ``reads`` = [(buffer offset,
+        file offset, bytes)]."""
+        rb = self.row_bytes
+        if self.n_rows == 0 or rb == 0:
+            return
+        per_batch = cap // rb
+        if per_batch < 1:
+            raise ValueError(f"SAI_AMD_INGEST_BUFFER of {cap} bytes is smaller than one row of {self.prefix}.bed ({rb} bytes)")
+        rows = self.file_row
+        new_range = np.empty(self.n_rows, dtype=bool)
+        new_range[0] = True
+        new_range[1:] = np.diff(rows) > 1 + _READ_THROUGH_BYTES // rb
+        if self.n_rows > 1 and bool((np.diff(rows) <= 0).any()):
+            raise ValueError(f"{self.prefix}.bim: the index is not in file order")
+        starts = np.flatnonzero(new_range)
+        range_first = rows[starts]  # first file row of every range
+        range_last = rows[np.append(starts[1:] - 1, self.n_rows - 1)]
+        range_base = np.concatenate(([0], np.cumsum(range_last - range_first + 1)))  # ... its place in the stream of all ranges
+        range_of = np.cumsum(new_range) - 1
+        stream_row = rows - range_first[range_of] + range_base[range_of]  # ascending
+        total = int(range_base[-1])
+        for lo in range(0, total, per_batch):
+            hi = min(lo + per_batch, total)
+            k0, k1 = (int(x) for x in np.searchsorted(stream_row, (lo, hi)))
+            reads = []
+            j = int(np.searchsorted(range_base, lo, side="right")) - 1
+            at = lo
+            while at < hi:
+                stop = min(hi, int(range_base[j + 1]))
+                reads.append(((at - lo) * rb, 3 + (int(range_first[j]) + at - int(range_base[j])) * rb, (stop - at) * rb))
+                at = stop
+                j += 1
+            yield k0, k1, (stream_row[k0:k1] - lo).astype(np.int32), hi - lo, reads
+
+    def raise_flagged(self, status: np.ndarray, row0: int = 0) -> None:
+        """The first flagged row of ``status`` (rows ``row0 ..`` of the index) as the reader's ValueError."""
+        bad = np.flatnonzero(status)
+        if bad.size == 0:
+            return
+        k, st = row0 + int(bad[0]), int(status[bad[0]])
+        if st == _ffi_plink.SAI_PLINK_STATUS_BAD_INDEX:
+            raise ValueError(f"{self.prefix}.bed: row {int(self.file_row[k])} was decoded with an index outside its range")
+        slot = self.n_slots - st
+        raise ValueError(
+            f"{self.prefix}.bed: heterozygous call of sample {self.samples[slot]} at variant {_variant_id(self.prefix, int(self.file_row[k]))} "
+            f"(position {int(self.pos[k])}), but the sample is configured with ploidy 1: a fileset has no phase to pick an allele by"
+        )
+
+
+def _variant_id(prefix: str, file_row: int) -> str:
+    """Column 2 of record line ``file_row`` of the ``.bim`` (error path only)."""
+    try:
+        with open(prefix + ".bim", "rb") as f:
+            k = -1
+            for line in f:
+                fields = line.split()
+                if fields:
+                    k += 1
+                    if k == file_row:
+                        return fields[1].decode("utf-8", "replace")
+    except (OSError, IndexError):
+        pass
+    return f"#{file_row + 1}"
+
+
+_pool = None
+
+
+def _read_pool() -> ThreadPoolExecutor:
+    global _pool
+    if _pool is None or getattr(_pool, "_owner", None) != os.getpid():  # threads do not survive a fork
+        _pool = ThreadPoolExecutor(max(1, min(default_threads(), 8)), thread_name_prefix="sai-plink-read")
+        _pool._owner = os.getpid()
+    return _pool
+
+
+def _pread_into(fd: int, view: memoryview, reads, path: str) -> None:
+    """Fill ``view`` from the file: ``reads`` = [(buffer offset, file offset, bytes)], large ones in pieces on
+    several threads (``preadv`` releases the GIL; one thread copies the page cache at a fraction of what PCIe takes)."""
+    pieces = []
+    for at, off, n in reads:
+        for d in range(0, n, _PREAD_PIECE):
+            pieces.append((at + d, off + d, min(_PREAD_PIECE, n - d)))
+
+    def one(piece):
+        at, off, n = piece
+        done = 0
+        while done < n:
+            got = os.preadv(fd, [view[at + done : at + n]], off + done)
+            if got <= 0:
+                raise ValueError(f"{path}: read error or unexpected end of file at byte {off + done}")
+            done += got
+
+    if len(pieces) > 1:
+        list(_read_pool().map(one, pieces))
+    else:
+        for piece in pieces:
+            one(piece)
+
+
+def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[int], start: Optional[int] = None,
+                end: Optional[int] = None, anc_allele_file: Optional[str] = None, n_threads: Optional[int] = None,
+                buffer_bytes: Optional[int] = None):  # fmt: skip
+    """(pos int32 [n], dosage int8 [n][len(samples)], n_matched, n_anc_entries) for one region, decoded on
+    the host (``sai_plink_decode_host``): the ``SAI_AMD_INGEST=host`` route and the yardstick of the kernel."""
+    lib = _ffi_plink.load_host()
+    n_threads = n_threads or default_threads()
+    idx = _Index(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads)
+    n = idx.n_slots
+    dos = np.empty((idx.n_rows, n), dtype=np.int8)
+    if n == 0 or idx.n_rows == 0:
+        return idx.pos, dos, idx.n_matched, idx.n_anc
+    cap = int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
+    status = np.empty(idx.n_rows, dtype=np.int32)
+    flip = idx.flip
+    buf = None
+    fd = os.open(idx.prefix + ".bed", os.O_RDONLY)
+    try:
+        for k0, k1, rib, n_batch_rows, reads in idx.batches(cap):
+            nbytes = n_batch_rows * idx.row_bytes
+            if buf is None or buf.size < nbytes:
+                buf = np.empty(nbytes, dtype=np.uint8)
+            _pread_into(fd, memoryview(buf), reads, idx.prefix + ".bed")
+            if k1 == k0:
+                continue
+            if lib.sai_plink_decode_host(
+                buf.ctypes.data_as(C.c_void_p), n_batch_rows, idx.row_bytes, k1 - k0, rib.ctypes.data_as(C.c_void_p),
+                flip[k0:k1].ctypes.data_as(C.c_void_p), idx.n_fam, n, idx.col_of_slot.ctypes.data_as(C.c_void_p),
+                idx.ploidies.ctypes.data_as(C.c_void_p), dos[k0:k1].ctypes.data_as(C.c_void_p),
+                status[k0:k1].ctypes.data_as(C.c_void_p), n_threads,
+            ):  # fmt: skip
+                raise _error(lib)
+    finally:
+        os.close(fd)
+    idx.raise_flagged(status)
+    return idx.pos, dos, idx.n_matched, idx.n_anc
+
+
+def _state(eng, cap: int) -> dict:
+    """Two pinned staging buffers, their device twins and the side stream, kept for the next call."""
+    import torch
+
+    st = eng.__dict__.setdefault("_plink_state", {})
+    if st.get("cap") != cap:
+        st.clear()
+        st["cap"] = cap
+        st["pinned"] = [torch.empty((cap,), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        st["rows"] = [torch.empty((cap,), dtype=torch.uint8, device=eng.device) for _ in range(2)]
+        st["stream"] = torch.cuda.Stream(device=eng.device)
+    return st
+
+
+def release_buffers(eng) -> None:
+    """Drop the staging ``load_dosage_device`` keeps between calls."""
+    st = eng.__dict__.pop("_plink_state", None)
+    if st:
+        st["stream"].synchronize()
+        st.clear()
+
+
+def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidies: Sequence[int],
+                       start: Optional[int] = None, end: Optional[int] = None, anc_allele_file: Optional[str] = None,
+                       n_threads: Optional[int] = None, buffer_bytes: Optional[int] = None, trace: Optional[dict] = None):  # fmt: skip
+    """(pos int32 host array [n], dosage int8 DEVICE tensor [n][len(samples)], n_matched, n_anc_entries):
+    ``load_dosage`` with the result left in HBM.  The selected rows are ``pread`` into two pinned buffers in
+    turn, copied on a side stream and decoded behind the copy, so the file read of batch k + 1 runs under
+    the copy and the kernel of batch k.  ``trace`` (a dict) collects host-clock seconds per phase: always
+    ``index`` and ``file_read``; with ``trace["serial"]`` set the side stream is synchronised behind every
+    copy and every kernel, so ``h2d`` and ``decode`` are timed on their own (and nothing overlaps)."""
+    import time
+
+    import torch
+
+    _ffi_plink.load()
+    lib = eng.lib
+    t0 = time.perf_counter()
+    idx = _Index(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads or default_threads())
+    if trace is not None:
+        trace["index"] = trace.get("index", 0.0) + time.perf_counter() - t0
+        trace["bed_bytes"] = 0
+    n = idx.n_slots
+    dos = torch.empty((idx.n_rows, n), dtype=torch.int8, device=eng.device)
+    if n == 0 or idx.n_rows == 0:
+        return idx.pos, dos, idx.n_matched, idx.n_anc
+    cap = int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
+    plan = idx.batches(cap)
+    first = next(plan)  # a buffer smaller than one row is refused before anything is page-locked
+    st = _state(eng, cap)
+    pinned, dev_rows, side = st["pinned"], st["rows"], st["stream"]
+    status = torch.empty((idx.n_rows,), dtype=torch.int32, device=eng.device)
+    cols_dev = None if idx.first_col >= 0 else torch.from_numpy(idx.col_of_slot).to(eng.device)
+    ploidy_dev = None if idx.uniform_ploidy else torch.from_numpy(idx.ploidies).to(eng.device)
+    copied = [None, None]  # per buffer: the event behind its last H2D copy
+    keep = []
+    fd = os.open(idx.prefix + ".bed", os.O_RDONLY)
+    try:
+        side.wait_stream(torch.cuda.current_stream(eng.device))  # `dos` and `status` were allocated on the current stream
+        b = 0
+
+        def batches():
+            yield first
+            yield from plan
+
+        for k0, k1, rib, n_batch_rows, reads in batches():
+            nbytes = n_batch_rows * idx.row_bytes
+            if copied[b] is not None:
+                copied[b].synchronize()  # the copy two batches back has left this pinned buffer
+            t1 = time.perf_counter()
+            _pread_into(fd, memoryview(pinned[b].numpy()), reads, idx.prefix + ".bed")
+            if trace is not None:
+                trace["file_read"] = trace.get("file_read", 0.0) + time.perf_counter() - t1
+                trace["bed_bytes"] += nbytes
+            serial = trace is not None and trace.get("serial")
+            with torch.cuda.stream(side):
+                t1 = time.perf_counter()
+                dev_rows[b][:nbytes].copy_(pinned[b][:nbytes], non_blocking=True)
+                copied[b] = torch.cuda.Event()
+                copied[b].record(side)
+                if serial:
+                    side.synchronize()
+                    trace["h2d"] = trace.get("h2d", 0.0) + time.perf_counter() - t1
+                    t1 = time.perf_counter()
+                if k1 > k0:
+                    d_rib = torch.from_numpy(rib).to(eng.device, non_blocking=True)
+                    d_flip = torch.from_numpy(idx.flip[k0:k1]).to(eng.device, non_blocking=True)
+                    keep.append((d_rib, d_flip))
+                    _ffi.check(
+                        lib.sai_plink_decode(eng.ctx, C.c_void_p(dev_rows[b].data_ptr()), n_batch_rows, idx.row_bytes, k1 - k0,
+                                             eng._ptr(d_rib), eng._ptr(d_flip), idx.n_fam, n, eng._ptr(cols_dev), idx.first_col,
+                                             eng._ptr(ploidy_dev), idx.uniform_ploidy, C.c_void_p(dos.data_ptr()), k0,
+                                             C.c_void_p(status.data_ptr() + 4 * k0), C.c_void_p(side.cuda_stream))
+                    )  # fmt: skip
+                if serial:
+                    side.synchronize()
+                    trace["decode"] = trace.get("decode", 0.0) + time.perf_counter() - t1
+            b ^= 1
+    finally:
+        os.close(fd)
+        side.synchronize()  # also on an error: the staging buffers are reused by the next call
+    flagged = status.cpu().numpy() if bool(status.any()) else None
+    if flagged is not None:
+        idx.raise_flagged(flagged)
+    torch.cuda.current_stream(eng.device).wait_stream(side)
+    return idx.pos, dos, idx.n_matched, idx.n_anc

@@ -42,9 +42,15 @@ def read_data(
     ``filter_missing`` = drop the sites where a sample of the population has a missing allele.  Blocks
     carry REF / ALT.  All options off and unphased is the ``score`` path's request: it goes to the native
     tokenizer (``read_dosage_data``: int8 dosages, REF / ALT not kept)."""
+    from .plink import is_fileset
+
     if not (is_phased or filter_ref or filter_tgt or filter_src or filter_out or filter_missing):
         return read_dosage_data(vcf_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
                                 anc_allele_file, start, end, engine)  # fmt: skip
+    if is_fileset(vcf_file):
+        # a fileset has neither phase nor REF / ALT columns to hand out: only the dosage request is served from it
+        raise ValueError(f"{vcf_file}: a PLINK fileset is read as unphased dosages only "
+                         "(is_phased=False and every filter_* option off); convert it to VCF for the other options")  # fmt: skip
     from .geno import load_population_data
 
     results = {}
@@ -174,10 +180,18 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
     tokenised on the GPU, ``device_vcf.load_dosage_device``) for all populations and ploidies, then one
     re-tiling launch per population straight from the shared [record][sample] block.  Returns
     ``(results, pos_dev)``: ``results`` as ``read_data`` gives it, except that every ``GT`` is a
-    ``TiledPop``; ``pos_dev`` = the int32 device copy of the positions (None without data)."""
+    ``TiledPop``; ``pos_dev`` = the int32 device copy of the positions (None without data).  A PLINK 1
+    fileset takes the same way with its own reader (``plink.load_dosage_device``: ``.bed`` rows over PCIe,
+    decoded on the GPU); there a slot is a (sample, ploidy) request, so one pass always serves all."""
     import torch
 
-    from .device_vcf import load_dosage_device
+    from . import plink
+
+    fileset = plink.is_fileset(vcf_file)
+    if fileset:
+        load_dosage_device = plink.load_dosage_device
+    else:
+        from .device_vcf import load_dosage_device
 
     chr_name = str(chr_name)
     groups = [("ref", ref_ind_file), ("tgt", tgt_ind_file), ("src", src_ind_file)]
@@ -206,7 +220,7 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
             ploidy = ploidy_config.root[group][population]
             for nme in pop_names:  # one output column per (sample, ploidy): the first occurrence keeps its place
                 if (nme, ploidy) not in column:
-                    k = next((i for i, p in enumerate(passes) if nme not in p["seen"]), len(passes))
+                    k = 0 if fileset and passes else next((i for i, p in enumerate(passes) if nme not in p["seen"]), len(passes))
                     if k == len(passes):
                         passes.append({"names": [], "ploidies": [], "seen": set()})
                     column[(nme, ploidy)] = (k, len(passes[k]["names"]))
@@ -219,7 +233,7 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
             results[group] = (None, samples_by_group[group])
         return results, None
     where = chr_name if start is None and end is None else f"{chr_name}:{start}-{end}"
-    if not os.path.exists(vcf_file):
+    if not fileset and not os.path.exists(vcf_file):
         raise ValueError(f"Failed to read VCF file {vcf_file} from {where}: cannot open VCF {vcf_file}")
     try:
         blocks = []
@@ -264,9 +278,13 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
 
 
 def _load_native(vcf_file, chr_name, names, ploidy, start, end, anc_allele_file):
-    """libsaihip's multithreaded tokenizer (sai_amd/csrc/vcf_ingest.cpp)."""
+    """libsaihip's multithreaded tokenizer (sai_amd/csrc/vcf_ingest.cpp), or its fileset reader
+    (sai_amd/csrc/plink) when the path names a PLINK 1 fileset."""
+    from . import plink
     from .native_vcf import load_dosage
 
+    if plink.is_fileset(vcf_file):
+        return plink.load_dosage(vcf_file, chr_name, names, [ploidy] * len(names), start, end, anc_allele_file)
     if not os.path.exists(vcf_file):
         raise ValueError(f"cannot open VCF {vcf_file}")
     return load_dosage(vcf_file, chr_name, names, [ploidy] * len(names), start, end, anc_allele_file)

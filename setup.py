@@ -24,7 +24,8 @@ def build_library() -> None:
         _build.build()
         dst = ROOT / "sai_amd" / "include"
         dst.mkdir(exist_ok=True)
-        shutil.copy2(ROOT / "include" / "saihip.h", dst / "saihip.h")  # travels as package data
+        for header in ("saihip.h", "saihip_plink.h"):
+            shutil.copy2(ROOT / "include" / header, dst / header)  # travel as package data
     finally:
         sys.path.remove(str(ROOT))
 
@@ -39,6 +40,21 @@ class DevelopWithLibrary(develop):
     def run(self):
         build_library()
         super().run()
+
+
+# on top of the table in pyproject.toml: the sources of the PLINK fileset reader live in a directory of their own
+EXTRA_PACKAGE_DATA = {"sai_amd": ["csrc/plink/*.hip", "csrc/plink/*.hpp", "csrc/plink/*.cpp"]}
+
+
+class WithExtraPackageData(setuptools.Distribution):
+    """Adds EXTRA_PACKAGE_DATA once the metadata (pyproject.toml, or the table below) has been read."""
+
+    def parse_config_files(self, *args, **kwargs):
+        super().parse_config_files(*args, **kwargs)
+        self.package_data = dict(self.package_data or {})
+        for package, patterns in EXTRA_PACKAGE_DATA.items():
+            have = list(self.package_data.get(package, []))
+            self.package_data[package] = have + [p for p in patterns if p not in have]
 
 
 def metadata_for_old_setuptools() -> dict:
@@ -60,4 +76,5 @@ def metadata_for_old_setuptools() -> dict:
     )  # fmt: skip
 
 
-setup(cmdclass={"build_py": BuildWithLibrary, "develop": DevelopWithLibrary}, **metadata_for_old_setuptools())
+setup(cmdclass={"build_py": BuildWithLibrary, "develop": DevelopWithLibrary}, distclass=WithExtraPackageData,
+      **metadata_for_old_setuptools())  # fmt: skip
