@@ -23,7 +23,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .. import _ffi, _ffi_plink
-from .native_vcf import default_threads
+from ._ingest import check_io, default_threads, pair, region_args, staging
 
 BUFFER_BYTES = 32 << 20  # as the VCF route (device_vcf.BUFFER_BYTES); SAI_AMD_INGEST_BUFFER overrides it
 _MAGIC = b"\x6c\x1b"
@@ -65,17 +65,12 @@ def _prefix_of(path) -> str:
     return text[: -len(".bed")] if text.endswith(".bed") else text
 
 
-def _error(lib) -> ValueError:
-    return ValueError(lib.sai_last_error().decode("utf-8", "replace"))
-
-
 def scan_first_last(path, chr_name: str):
     """First and last position of the first contiguous run of ``chr_name`` in the ``.bim`` (None, None if
     absent): ``native_vcf.scan_first_last`` for a fileset."""
     lib = _ffi_plink.load_host()
     first, last = C.c_int64(-1), C.c_int64(-1)
-    if lib.sai_plink_scan(os.fsencode(_prefix_of(path)), str(chr_name).encode(), C.byref(first), C.byref(last)):
-        raise _error(lib)
+    check_io(lib, lib.sai_plink_scan(os.fsencode(_prefix_of(path)), str(chr_name).encode(), C.byref(first), C.byref(last)))
     return (None, None) if first.value < 0 else (int(first.value), int(last.value))
 
 
@@ -85,26 +80,19 @@ class _Index:
 
     def __init__(self, lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads):
         self.prefix = _prefix_of(path)
-        n = len(samples)
-        names = (C.c_char_p * n)(*[s.encode() for s in samples])
-        pl = (C.c_int32 * n)(*[int(p) for p in ploidies])
-        handle = C.c_void_p()
-        if lib.sai_plink_open(
-            os.fsencode(self.prefix), str(chr_name).encode(), -1 if start is None else int(start), -1 if end is None else int(end),
-            n, names, pl, os.fsencode(anc_allele_file) if anc_allele_file else None, n_threads or default_threads(), C.byref(handle),
-        ):  # fmt: skip
-            raise _error(lib)
+        n, handle = len(samples), C.c_void_p()
+        args = region_args(self.prefix, chr_name, start, end, samples, ploidies, anc_allele_file, n_threads)
+        check_io(lib, lib.sai_plink_open(*args, C.byref(handle)))
         try:
             v = [C.c_int64() for _ in range(8)]
-            if lib.sai_plink_index_info(handle, *[C.byref(x) for x in v]):
-                raise _error(lib)
+            check_io(lib, lib.sai_plink_index_info(handle, *[C.byref(x) for x in v]))
             n_rows, self.n_matched, self.n_anc, self.row_bytes, self.n_fam, self.n_bim, self.first, self.last = (int(x.value) for x in v)
             self.pos = np.empty(n_rows, dtype=np.int32)
             self.file_row = np.empty(n_rows, dtype=np.int64)
             self.flip = np.empty(n_rows, dtype=np.uint8)
             self.col_of_slot = np.empty(n, dtype=np.int32)
-            if lib.sai_plink_index_copy(handle, *(a.ctypes.data_as(C.c_void_p) for a in (self.pos, self.file_row, self.flip, self.col_of_slot))):
-                raise _error(lib)
+            arrays = (self.pos, self.file_row, self.flip, self.col_of_slot)
+            check_io(lib, lib.sai_plink_index_copy(handle, *(a.ctypes.data_as(C.c_void_p) for a in arrays)))
         finally:
             lib.sai_plink_index_close(handle)
         self.samples = list(samples)
@@ -244,31 +232,16 @@ def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[
             _pread_into(fd, memoryview(buf), reads, idx.prefix + ".bed")
             if k1 == k0:
                 continue
-            if lib.sai_plink_decode_host(
+            check_io(lib, lib.sai_plink_decode_host(
                 buf.ctypes.data_as(C.c_void_p), n_batch_rows, idx.row_bytes, k1 - k0, rib.ctypes.data_as(C.c_void_p),
                 flip[k0:k1].ctypes.data_as(C.c_void_p), idx.n_fam, n, idx.col_of_slot.ctypes.data_as(C.c_void_p),
                 idx.ploidies.ctypes.data_as(C.c_void_p), dos[k0:k1].ctypes.data_as(C.c_void_p),
                 status[k0:k1].ctypes.data_as(C.c_void_p), n_threads,
-            ):  # fmt: skip
-                raise _error(lib)
+            ))  # fmt: skip
     finally:
         os.close(fd)
     idx.raise_flagged(status)
     return idx.pos, dos, idx.n_matched, idx.n_anc
-
-
-def _state(eng, cap: int) -> dict:
-    """Two pinned staging buffers, their device twins and the side stream, kept for the next call."""
-    import torch
-
-    st = eng.__dict__.setdefault("_plink_state", {})
-    if st.get("cap") != cap:
-        st.clear()
-        st["cap"] = cap
-        st["pinned"] = [torch.empty((cap,), dtype=torch.uint8).pin_memory() for _ in range(2)]
-        st["rows"] = [torch.empty((cap,), dtype=torch.uint8, device=eng.device) for _ in range(2)]
-        st["stream"] = torch.cuda.Stream(device=eng.device)
-    return st
 
 
 def release_buffers(eng) -> None:
@@ -295,7 +268,7 @@ def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidie
     _ffi_plink.load()
     lib = eng.lib
     t0 = time.perf_counter()
-    idx = _Index(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads or default_threads())
+    idx = _Index(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads)
     if trace is not None:
         trace["index"] = trace.get("index", 0.0) + time.perf_counter() - t0
         trace["bed_bytes"] = 0
@@ -306,7 +279,9 @@ def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidie
     cap = int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
     plan = idx.batches(cap)
     first = next(plan)  # a buffer smaller than one row is refused before anything is page-locked
-    st = _state(eng, cap)
+    # two pinned staging buffers, their device twins and the side stream, kept for the next call
+    st = staging(eng, "_plink_state", cap, lambda: {"pinned": pair(cap), "rows": pair(cap, device=eng.device),
+                                                    "stream": torch.cuda.Stream(device=eng.device)})  # fmt: skip
     pinned, dev_rows, side = st["pinned"], st["rows"], st["stream"]
     status = torch.empty((idx.n_rows,), dtype=torch.int32, device=eng.device)
     cols_dev = None if idx.first_col >= 0 else torch.from_numpy(idx.col_of_slot).to(eng.device)

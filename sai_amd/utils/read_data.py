@@ -88,12 +88,54 @@ def read_dosage_data(
     the Python statement of the same rules (``engine="python"``, used by the tests as the
     cross-check); REF/ALT are not kept (nothing reads them after polarisation)."""
     chr_name = str(chr_name)
+    samples_by_group = _parse_groups(ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file)
+    # one pass per distinct ploidy (normally one or two), each over the samples that need it
+    by_ploidy: dict[int, list[str]] = {}
+    seen: dict[int, set[str]] = {}
+    for _, names, ploidy in _wanted(samples_by_group, ploidy_config):
+        bucket, have = by_ploidy.setdefault(ploidy, []), seen.setdefault(ploidy, set())
+        for n in names:  # first occurrence keeps its place (a sample may sit in several populations)
+            if n not in have:
+                have.add(n)
+                bucket.append(n)
+    if not any(by_ploidy.values()):
+        return {"outgroup": (None, None), **{group: (None, samples) for group, samples in samples_by_group.items()}}
+
+    loader = _load_python if engine == "python" else _load_native
+    where = chr_name if start is None and end is None else f"{chr_name}:{start}-{end}"
+    loaded = {}
+    for ploidy, names in by_ploidy.items():
+        try:
+            pos, dos, n_matched, n_anc = loader(vcf_file, chr_name, names, ploidy, start, end, anc_allele_file)
+        except FileNotFoundError:
+            raise
+        except Exception as e:  # utils.py:139-140
+            raise ValueError(f"Failed to read VCF file {vcf_file} from {where}: {e}") from e
+        _check_anc_found(anc_allele_file, n_matched, n_anc, chr_name, start, end)
+        loaded[ploidy] = (pos, dos, {n: i for i, n in enumerate(names)}, n_matched)
+
+    def block(population, names, ploidy):
+        pos, dos, column, n_matched = loaded[ploidy]
+        if n_matched == 0:  # no record in the region: the reference's "vcf_data is None" case
+            return None
+        cols = [column[n] for n in names]
+        if cols and cols == list(range(cols[0], cols[0] + len(cols))):  # the usual case: one block of columns
+            gt = np.ascontiguousarray(dos[:, cols[0] : cols[0] + len(cols)])
+        else:
+            gt = np.ascontiguousarray(dos[:, cols])
+        return ChromosomeData(POS=pos.copy(), REF=None, ALT=None, GT=gt)
+
+    return _assemble(samples_by_group, ploidy_config, block)
+
+
+def _parse_groups(ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file) -> dict:
+    """group -> {population: sample names} (None for a group without a sample file), in the order ref, tgt, src,
+    outgroup; every population with a ploidy entry must be in its group's sample file."""
     groups = [("ref", ref_ind_file), ("tgt", tgt_ind_file), ("src", src_ind_file)]
     # utils.py:331-337: an outgroup file only counts when the ploidy section names outgroups
     if out_ind_file is not None and "outgroup" in ploidy_config.root:
         groups.append(("outgroup", out_ind_file))
     samples_by_group: dict[str, Optional[dict[str, list[str]]]] = {}
-    wanted: set[str] = set()
     for group, ind_file in groups:
         if ind_file is None:
             samples_by_group[group] = None
@@ -107,49 +149,29 @@ def read_dosage_data(
                     f"Population '{population}' in ploidy_config[{group}] not found in sample file: {ind_file}"
                 )
         samples_by_group[group] = samples
-        for population, names in samples.items():
-            if population in ploidy_config.root[group]:
-                wanted.update(names)
+    return samples_by_group
 
+
+def _wanted(samples_by_group, ploidy_config):
+    """(population, sample names, ploidy) of every population that has a ploidy entry, in file order."""
+    for group, samples in samples_by_group.items():
+        for population, names in (samples or {}).items():
+            if population in ploidy_config.root[group]:
+                yield population, names, ploidy_config.root[group][population]
+
+
+def _check_anc_found(anc_allele_file, n_matched, n_anc, chr_name, start, end) -> None:
+    if anc_allele_file and n_matched and n_anc == 0:  # read_anc_allele, utils.py:480-487
+        if start is not None or end is not None:
+            raise ValueError(f"No ancestral allele is found for chromosome {chr_name} in the region {start}-{end}.")
+        raise ValueError(f"No ancestral allele is found for chromosome {chr_name}.")
+
+
+def _assemble(samples_by_group, ploidy_config, block) -> dict:
+    """The readers' result: ``block(population, names, ploidy)`` gives the ChromosomeData of a population (None when
+    the region holds no record); a population without a ploidy entry is skipped with the reference's RuntimeWarning."""
     results: dict = {"outgroup": (None, None)}
-    if not wanted:
-        for group, _ in groups:
-            results[group] = (None, samples_by_group[group])
-        return results
-
-    loader = _load_python if engine == "python" else _load_native
-    where = chr_name if start is None and end is None else f"{chr_name}:{start}-{end}"
-    # one pass per distinct ploidy (normally one or two), each over the samples that need it
-    by_ploidy: dict[int, list[str]] = {}
-    seen: dict[int, set[str]] = {}
-    for group, _ in groups:
-        samples = samples_by_group[group]
-        if samples is None:
-            continue
-        for population, names in samples.items():
-            if population in ploidy_config.root[group]:
-                ploidy = ploidy_config.root[group][population]
-                bucket, have = by_ploidy.setdefault(ploidy, []), seen.setdefault(ploidy, set())
-                for n in names:  # first occurrence keeps its place (a sample may sit in several populations)
-                    if n not in have:
-                        have.add(n)
-                        bucket.append(n)
-    loaded = {}
-    for ploidy, names in by_ploidy.items():
-        try:
-            pos, dos, n_matched, n_anc = loader(vcf_file, chr_name, names, ploidy, start, end, anc_allele_file)
-        except FileNotFoundError:
-            raise
-        except Exception as e:  # utils.py:139-140
-            raise ValueError(f"Failed to read VCF file {vcf_file} from {where}: {e}") from e
-        if anc_allele_file and n_matched and n_anc == 0:  # read_anc_allele, utils.py:480-487
-            if start is not None or end is not None:
-                raise ValueError(f"No ancestral allele is found for chromosome {chr_name} in the region {start}-{end}.")
-            raise ValueError(f"No ancestral allele is found for chromosome {chr_name}.")
-        loaded[ploidy] = (pos, dos, {n: i for i, n in enumerate(names)}, n_matched)
-
-    for group, _ in groups:
-        samples = samples_by_group[group]
+    for group, samples in samples_by_group.items():
         if samples is None:
             results[group] = (None, None)
             continue
@@ -161,15 +183,9 @@ def read_dosage_data(
                     RuntimeWarning,
                 )
                 continue
-            pos, dos, column, n_matched = loaded[ploidy_config.root[group][population]]
-            if n_matched == 0:  # no record in the region: the reference's "vcf_data is None" case
-                continue
-            cols = [column[n] for n in names]
-            if cols and cols == list(range(cols[0], cols[0] + len(cols))):  # the usual case: one block of columns
-                gt = np.ascontiguousarray(dos[:, cols[0] : cols[0] + len(cols)])
-            else:
-                gt = np.ascontiguousarray(dos[:, cols])
-            data[population] = ChromosomeData(POS=pos.copy(), REF=None, ALT=None, GT=gt)
+            got = block(population, names, ploidy_config.root[group][population])
+            if got is not None:
+                data[population] = got
         results[group] = (data if data else None, samples)
     return results
 
@@ -194,44 +210,23 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
         from .device_vcf import load_dosage_device
 
     chr_name = str(chr_name)
-    groups = [("ref", ref_ind_file), ("tgt", tgt_ind_file), ("src", src_ind_file)]
-    if out_ind_file is not None and "outgroup" in ploidy_config.root:
-        groups.append(("outgroup", out_ind_file))
+    samples_by_group = _parse_groups(ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file)
     # One streaming pass maps a VCF column to ONE output slot, so a sample that sits in populations of
     # different ploidy (the reference reads every population on its own, with its own ploidy:
     # utils.py:123-138) is tokenised in a further pass: passes[k] holds each sample at most once.
-    samples_by_group, column, passes = {}, {}, []
-    for group, ind_file in groups:
-        if ind_file is None:
-            samples_by_group[group] = None
-            continue
-        samples = parse_ind_file(ind_file)
-        if group not in ploidy_config.root:
-            raise ValueError(f"Ploidy configuration missing group '{group}'.")
-        for population in ploidy_config.root[group]:
-            if population not in samples:
-                raise ValueError(
-                    f"Population '{population}' in ploidy_config[{group}] not found in sample file: {ind_file}"
-                )
-        samples_by_group[group] = samples
-        for population, pop_names in samples.items():
-            if population not in ploidy_config.root[group]:
-                continue
-            ploidy = ploidy_config.root[group][population]
-            for nme in pop_names:  # one output column per (sample, ploidy): the first occurrence keeps its place
-                if (nme, ploidy) not in column:
-                    k = 0 if fileset and passes else next((i for i, p in enumerate(passes) if nme not in p["seen"]), len(passes))
-                    if k == len(passes):
-                        passes.append({"names": [], "ploidies": [], "seen": set()})
-                    column[(nme, ploidy)] = (k, len(passes[k]["names"]))
-                    passes[k]["names"].append(nme)
-                    passes[k]["ploidies"].append(ploidy)
-                    passes[k]["seen"].add(nme)
-    results: dict = {"outgroup": (None, None)}
+    column, passes = {}, []
+    for _, pop_names, ploidy in _wanted(samples_by_group, ploidy_config):
+        for nme in pop_names:  # one output column per (sample, ploidy): the first occurrence keeps its place
+            if (nme, ploidy) not in column:
+                k = 0 if fileset and passes else next((i for i, p in enumerate(passes) if nme not in p["seen"]), len(passes))
+                if k == len(passes):
+                    passes.append({"names": [], "ploidies": [], "seen": set()})
+                column[(nme, ploidy)] = (k, len(passes[k]["names"]))
+                passes[k]["names"].append(nme)
+                passes[k]["ploidies"].append(ploidy)
+                passes[k]["seen"].add(nme)
     if not passes:
-        for group, _ in groups:
-            results[group] = (None, samples_by_group[group])
-        return results, None
+        return {"outgroup": (None, None), **{group: (None, samples) for group, samples in samples_by_group.items()}}, None
     where = chr_name if start is None and end is None else f"{chr_name}:{start}-{end}"
     if not fileset and not os.path.exists(vcf_file):
         raise ValueError(f"Failed to read VCF file {vcf_file} from {where}: cannot open VCF {vcf_file}")
@@ -245,36 +240,21 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
         raise
     except Exception as e:  # utils.py:139-140
         raise ValueError(f"Failed to read VCF file {vcf_file} from {where}: {e}") from e
-    if anc_allele_file and n_matched and n_anc == 0:  # read_anc_allele, utils.py:480-487
-        if start is not None or end is not None:
-            raise ValueError(f"No ancestral allele is found for chromosome {chr_name} in the region {start}-{end}.")
-        raise ValueError(f"No ancestral allele is found for chromosome {chr_name}.")
+    _check_anc_found(anc_allele_file, n_matched, n_anc, chr_name, start, end)
+
+    def block(population, pop_names, ploidy):
+        if n_matched == 0:
+            return None
+        where_cols = [column[(nme, ploidy)] for nme in pop_names]
+        used = {k for k, _ in where_cols}
+        if len(used) == 1:
+            tiled = eng.tile_columns(blocks[used.pop()], [c for _, c in where_cols])
+        else:  # the population's samples were tokenised in different passes: gather its columns first
+            tiled = eng._tile_device(torch.stack([blocks[k][:, c] for k, c in where_cols], dim=1).contiguous())
+        return ChromosomeData(POS=pos, REF=None, ALT=None, GT=tiled)
+
     pos_dev = torch.from_numpy(pos).to(eng.device) if n_matched else None
-    for group, _ in groups:
-        samples = samples_by_group[group]
-        if samples is None:
-            results[group] = (None, None)
-            continue
-        data: dict[str, ChromosomeData] = {}
-        for population, pop_names in samples.items():
-            if population not in ploidy_config.root[group]:
-                warnings.warn(
-                    f"Population '{population}' found in sample file but not in ploidy_config[{group}]; skipping.",
-                    RuntimeWarning,
-                )
-                continue
-            if n_matched == 0:
-                continue
-            ploidy = ploidy_config.root[group][population]
-            where_cols = [column[(nme, ploidy)] for nme in pop_names]
-            used = {k for k, _ in where_cols}
-            if len(used) == 1:
-                tiled = eng.tile_columns(blocks[used.pop()], [c for _, c in where_cols])
-            else:  # the population's samples were tokenised in different passes: gather its columns first
-                tiled = eng._tile_device(torch.stack([blocks[k][:, c] for k, c in where_cols], dim=1).contiguous())
-            data[population] = ChromosomeData(POS=pos, REF=None, ALT=None, GT=tiled)
-        results[group] = (data if data else None, samples)
-    return results, pos_dev
+    return _assemble(samples_by_group, ploidy_config, block), pos_dev
 
 
 def _load_native(vcf_file, chr_name, names, ploidy, start, end, anc_allele_file):
