@@ -38,17 +38,18 @@ def deflate(data: bytes, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, flush_every=
     return out + c.flush()
 
 
-def run(eng, streams, texts, rng=None, gap=0, text_gap=0):
+def run(eng, streams, texts, rng=None, gap=0, text_gap=0, crcs=None, info=None):
     """Inflate `streams` (raw deflate) placed one after the other (+ `gap` random bytes between them)
     into a text buffer with `text_gap` guard bytes between the outputs.  Returns (status, outputs,
-    guards_intact)."""
+    guards_intact).  `crcs`: the CRC-32 values of the trailers where they are not to be those of
+    `texts`; `info`: a dict that receives the address of the text buffer and the member table."""
     import torch
 
     comp, table, off, out_off = bytearray(), np.zeros(len(streams), dtype=MEMBER), 0, text_gap
     for i, (s, t) in enumerate(zip(streams, texts)):
         pad = bytes(rng.integers(0, 256, size=gap, dtype=np.uint8)) if (rng is not None and gap) else b""
         comp += pad
-        table[i] = (len(comp), out_off, len(s), len(t), zlib.crc32(t), 0)
+        table[i] = (len(comp), out_off, len(s), len(t), zlib.crc32(t) if crcs is None else crcs[i], 0)
         comp += s
         out_off += len(t) + text_gap
     comp += b"\0" * (-len(comp) % 4 + 4)
@@ -62,6 +63,8 @@ def run(eng, streams, texts, rng=None, gap=0, text_gap=0):
     _ffi.check(eng.lib.sai_inflate_bgzf(eng.ctx, C.c_void_p(d_comp.data_ptr()), d_comp.numel(), C.c_void_p(d_tab.data_ptr()),
                                         len(streams), C.c_void_p(d_text.data_ptr()), n_text, C.c_void_p(d_stat.data_ptr()), None))  # fmt: skip
     torch.cuda.synchronize()
+    if info is not None:
+        info.update(text_ptr=d_text.data_ptr(), table=table)
     text = d_text.cpu().numpy()
     outs, guards = [], True
     prev_end = 0
@@ -110,7 +113,7 @@ def test_every_block_type_and_shape(eng):
     add(bytes(rng.integers(0, 256, size=2000, dtype=np.uint8)) * 30)  # long matches at distance 2000
     period = bytes(rng.integers(0, 256, size=32768, dtype=np.uint8))
     add(period + period)  # matches at distance 32768, the far end of the window
-    add(period[:20000] * 3 + period[:5536])  # distances beyond the 16 KiB kept in LDS: served from the text in HBM
+    add(period[:20000] * 3 + period[:5536])  # distances beyond the history kept in LDS (4 KiB by default): served from the text in HBM
     mix = bytearray(vcf_like(rng, 65536))
     for _ in range(40):  # far and near matches interleaved
         o = int(rng.integers(0, 30000))
