@@ -8,213 +8,33 @@
 // (what `plink2 --make-bed` and `plink --keep-allele-order` write from a VCF): rows of the chromosome
 // inside [start, end] in file order; with an ancestral-allele file only listed sites are kept, a site
 // whose ancestral allele is A1 is flipped, one whose ancestral allele is neither is dropped -- the
-// decision of parse_lines() in ingest_base.hpp, restated in anc_decision() below.
+// decision of parse_lines() in ingest_base.hpp, restated in anc_decision() of fileset_index.hpp, which also holds the
+// passes over the .fam and the .bim (shared with the EIGENSTRAT reader).
 
-#include <sys/mman.h>
-
-#include "../ingest_base.hpp"
+#include "fileset_index.hpp"
 #include "plink_codes.hpp"
 #include "saihip_plink.h"
 
 struct sai_plink_index {
-  std::vector<int32_t> pos;
-  std::vector<int64_t> file_row;  // 0-based row of the .bed (= record line of the .bim)
-  std::vector<uint8_t> flip;
+  VariantRows rows;  // file_row = 0-based row of the .bed (= record line of the .bim)
   std::vector<int32_t> col_of_slot;
-  int64_t n_matched = 0;
   int64_t n_anc_entries = 0;
   int64_t row_bytes = 0;
   int64_t n_fam = 0;
-  int64_t n_bim = 0;
-  int64_t first = -1, last = -1;  // the first contiguous run of the chromosome, whole file
 };
 
 namespace {
 
-struct MappedFile {
-  const char* data = nullptr;
-  size_t size = 0;
-  bool ok = false;
-  explicit MappedFile(const std::string& path) {
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) return;
-    struct stat sb;
-    if (fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode)) {
-      size = static_cast<size_t>(sb.st_size);
-      ok = true;
-      if (size) {
-        void* p = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (p == MAP_FAILED) ok = false;
-        else data = static_cast<const char*>(p);
-      }
-    }
-    close(fd);
-  }
-  ~MappedFile() {
-    if (data) munmap(const_cast<char*>(data), size);
-  }
-  MappedFile(const MappedFile&) = delete;
-  MappedFile& operator=(const MappedFile&) = delete;
-};
-
-inline bool is_blank(char c) { return c == ' ' || c == '\t' || c == '\r'; }
-
-// up to `want` blank-separated tokens of [p, eol); returns how many were found
-inline int split_tokens(const char* p, const char* eol, int want, const char** tok, size_t* len) {
-  int found = 0;
-  while (found < want) {
-    while (p < eol && is_blank(*p)) ++p;
-    if (p >= eol) break;
-    const char* s = p;
-    while (p < eol && !is_blank(*p)) ++p;
-    tok[found] = s;
-    len[found] = static_cast<size_t>(p - s);
-    ++found;
-  }
-  return found;
-}
-
-enum AncDecision { kDrop = 0, kKeep = 1, kFlip = 2 };
-
-// ingest_base.hpp, parse_lines(): not listed -> drop; the ancestral allele equals ALT (A1) -> flip;
-// else equals REF (A2) -> keep; else drop
-inline AncDecision anc_decision(const AncMap& anc, int64_t pos, const char* a1, size_t n1, const char* a2, size_t n2) {
-  if (!anc.active) return kKeep;
-  const auto it = anc.allele.find(pos);
-  if (it == anc.allele.end()) return kDrop;
-  const AncAllele& a = it->second;
-  if (a.size() == n1 && memcmp(a.data(), a1, n1) == 0) return kFlip;
-  if (a.size() == n2 && memcmp(a.data(), a2, n2) == 0) return kKeep;
-  return kDrop;
-}
-
-struct BimPiece {
-  int64_t n_lines = 0;  // record lines (blank lines are not rows)
-  int64_t matched = 0;
-  std::vector<int32_t> pos;
-  std::vector<int64_t> row;  // counted from the piece's first record line
-  std::vector<uint8_t> flip;
-  int64_t first = -1, last = -1;  // the first run of the chromosome inside the piece
-  bool other_before = false, ended = false;
-  int64_t bad_line = -1;  // a line with fewer than six columns (piece-relative)
-  bool failed = false;    // out of memory
-};
-
-void bim_piece(const char* p, const char* end, const std::string& chrom, int64_t start, int64_t stop, const AncMap& anc,
-               bool want_rows, BimPiece& out) {
-  while (p < end) {
-    const char* eol = static_cast<const char*>(memchr(p, '\n', static_cast<size_t>(end - p)));
-    if (!eol) eol = end;
-    const char* tok[6];
-    size_t len[6];
-    const int found = split_tokens(p, eol, 6, tok, len);
-    p = eol + 1;
-    if (found == 0) continue;
-    const int64_t line = out.n_lines++;
-    if (found < 6) {
-      out.bad_line = line;
-      return;
-    }
-    if (len[0] != chrom.size() || memcmp(tok[0], chrom.data(), chrom.size()) != 0) {
-      if (out.first >= 0) out.ended = true;
-      else out.other_before = true;
-      continue;
-    }
-    int64_t pos = 0;
-    for (const char* f = tok[3]; f < tok[3] + len[3] && *f >= '0' && *f <= '9'; ++f) pos = pos * 10 + (*f - '0');
-    if (!out.ended) {
-      if (out.first < 0) out.first = pos;
-      out.last = pos;
-    }
-    if ((start >= 0 && pos < start) || (stop >= 0 && pos > stop)) continue;
-    ++out.matched;
-    if (!want_rows) continue;
-    const AncDecision d = anc_decision(anc, pos, tok[4], len[4], tok[5], len[5]);
-    if (d == kDrop) continue;
-    out.pos.push_back(static_cast<int32_t>(pos));
-    out.row.push_back(line);
-    out.flip.push_back(d == kFlip ? 1 : 0);
-  }
-}
-
-// One pass over PREFIX.bim, split over n_threads at line boundaries; fills the row part of `idx`.
-int bim_pass(const std::string& path, const std::string& chrom, int64_t start, int64_t stop, const AncMap& anc,
-             bool want_rows, int n_threads, sai_plink_index& idx) {
-  MappedFile bim(path);
-  if (!bim.ok) return sai_set_error(SAI_ERR_ARG, "cannot open %s", path.c_str());
-  const char* base = bim.data;
-  const size_t total = bim.size;
-  const int nt = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(std::max(n_threads, 1)), total / (size_t(1) << 20) + 1)));
-  std::vector<size_t> edge(static_cast<size_t>(nt) + 1, total);
-  edge[0] = 0;
-  for (int t = 1; t < nt; ++t) {
-    const size_t guess = std::max(edge[static_cast<size_t>(t) - 1], total * static_cast<size_t>(t) / static_cast<size_t>(nt));
-    const void* nl = guess < total ? memchr(base + guess, '\n', total - guess) : nullptr;
-    edge[static_cast<size_t>(t)] = nl ? static_cast<size_t>(static_cast<const char*>(nl) - base) + 1 : total;
-  }
-  std::vector<BimPiece> pieces(static_cast<size_t>(nt));
-  auto work = [&](int t) {  // an exception must not leave a worker thread
-    BimPiece& pc = pieces[static_cast<size_t>(t)];
-    try {
-      if (total) bim_piece(base + edge[static_cast<size_t>(t)], base + edge[static_cast<size_t>(t) + 1], chrom, start, stop, anc, want_rows, pc);
-    } catch (...) {
-      pc.failed = true;
-    }
-  };
-  {
-    ThreadGroup tg;
-    for (int t = 1; t < nt; ++t) tg.spawn([&work, t] { work(t); });
-    work(0);
-    tg.join();
-  }
-  int64_t line0 = 0;
-  size_t n_rows = 0;
-  for (const BimPiece& pc : pieces) {
-    if (pc.failed) return sai_set_error(SAI_ERR_HIP, "%s: out of host memory", path.c_str());
-    if (pc.bad_line >= 0)
-      return sai_set_error(SAI_ERR_ARG, "%s: variant line %lld has fewer than 6 columns", path.c_str(),
-                           static_cast<long long>(line0 + pc.bad_line + 1));
-    line0 += pc.n_lines;
-    n_rows += pc.pos.size();
-  }
-  idx.n_bim = line0;
-  idx.pos.reserve(n_rows);
-  idx.file_row.reserve(n_rows);
-  idx.flip.reserve(n_rows);
-  line0 = 0;
-  bool run_over = false;
-  for (const BimPiece& pc : pieces) {  // in file order
-    idx.n_matched += pc.matched;
-    idx.pos.insert(idx.pos.end(), pc.pos.begin(), pc.pos.end());
-    for (int64_t r : pc.row) idx.file_row.push_back(line0 + r);
-    idx.flip.insert(idx.flip.end(), pc.flip.begin(), pc.flip.end());
-    line0 += pc.n_lines;
-    if (run_over) continue;
-    if (idx.first < 0) {
-      if (pc.first >= 0) {
-        idx.first = pc.first;
-        idx.last = pc.last;
-        run_over = pc.ended;
-      }
-    } else if (pc.other_before) {
-      run_over = true;  // the run ended where the previous piece ended
-    } else if (pc.first >= 0) {
-      idx.last = pc.last;
-      run_over = pc.ended;
-    } else if (pc.ended) {
-      run_over = true;
-    }
-  }
-  return SAI_OK;
-}
+// .bim: chromosome, id, genetic position, position, A1 (plays ALT), A2 (plays REF)
+constexpr VariantLayout kBimLayout = {0, 3, 5, 4, 6, false, false};
 
 int plink_scan_impl(const char* prefix, const char* chrom, int64_t* first_pos, int64_t* last_pos) {
   if (!prefix || !chrom || !first_pos || !last_pos) return sai_set_error(SAI_ERR_ARG, "NULL argument");
-  sai_plink_index idx;
+  VariantRows rows;
   AncMap none;
-  if (int rc = bim_pass(std::string(prefix) + ".bim", chrom, -1, -1, none, false, kScanThreads, idx)) return rc;
-  *first_pos = idx.first;
-  *last_pos = idx.last;
+  if (int rc = variant_pass(std::string(prefix) + ".bim", kBimLayout, chrom, -1, -1, none, false, kScanThreads, rows)) return rc;
+  *first_pos = rows.first;
+  *last_pos = rows.last;
   return SAI_OK;
 }
 
@@ -232,45 +52,14 @@ int plink_open_impl(const char* prefix, const char* chrom, int64_t start, int64_
   const std::string pre(prefix), c(chrom);
   std::unique_ptr<sai_plink_index> holder(new sai_plink_index);
   sai_plink_index& idx = *holder;
-  {  // .fam: one sample per record line, the name is column 2 (IID)
-    const std::string path = pre + ".fam";
-    MappedFile fam(path);
-    if (!fam.ok) return sai_set_error(SAI_ERR_ARG, "cannot open %s", path.c_str());
-    std::unordered_map<std::string, std::pair<int32_t, bool>> col_of;  // name -> (first column, seen again)
-    const char* p = fam.data;
-    const char* endp = fam.data + fam.size;
-    int64_t n = 0;
-    while (p < endp) {
-      const char* eol = static_cast<const char*>(memchr(p, '\n', static_cast<size_t>(endp - p)));
-      if (!eol) eol = endp;
-      const char* tok[2];
-      size_t len[2];
-      const int found = split_tokens(p, eol, 2, tok, len);
-      p = eol + 1;
-      if (found == 0) continue;
-      if (found < 2) return sai_set_error(SAI_ERR_ARG, "%s: sample line %lld has fewer than 2 columns", path.c_str(), static_cast<long long>(n + 1));
-      if (n >= 0x7FFFFFFF) return sai_set_error(SAI_ERR_UNSUPPORTED, "%s: too many samples", path.c_str());
-      if (n_samples > 0) {
-        auto ins = col_of.emplace(std::string(tok[1], len[1]), std::make_pair(static_cast<int32_t>(n), false));
-        if (!ins.second) ins.first->second.second = true;
-      }
-      ++n;
-    }
-    idx.n_fam = n;
-    idx.row_bytes = (n + 3) / 4;
-    idx.col_of_slot.resize(static_cast<size_t>(n_samples));
-    for (int32_t s = 0; s < n_samples; ++s) {
-      const auto it = col_of.find(sample_names[s]);
-      if (it == col_of.end()) return sai_set_error(SAI_ERR_ARG, "samples not found in %s: %s", path.c_str(), sample_names[s]);
-      if (it->second.second) return sai_set_error(SAI_ERR_ARG, "sample %s occurs twice in %s", sample_names[s], path.c_str());
-      idx.col_of_slot[static_cast<size_t>(s)] = it->second.first;
-    }
-  }
+  // .fam: one sample per record line, the name is column 2 (IID)
+  if (int rc = resolve_samples(pre + ".fam", 1, false, n_samples, sample_names, idx.col_of_slot, &idx.n_fam)) return rc;
+  idx.row_bytes = (idx.n_fam + 3) / 4;
   AncMap anc;
   if (anc_bed_path) {
     if (int rc = load_anc(anc_bed_path, c, start, end, anc, &idx.n_anc_entries)) return rc;
   }
-  if (int rc = bim_pass(pre + ".bim", c, start, end, anc, true, n_threads, idx)) return rc;
+  if (int rc = variant_pass(pre + ".bim", kBimLayout, c, start, end, anc, true, n_threads, idx.rows)) return rc;
   {  // .bed: magic, variant-major, exactly one row per .bim line
     const std::string path = pre + ".bed";
     const int fd = open(path.c_str(), O_RDONLY);
@@ -286,10 +75,10 @@ int plink_open_impl(const char* prefix, const char* chrom, int64_t start, int64_
       return sai_set_error(SAI_ERR_UNSUPPORTED, "%s: sample-major .bed files are not supported (third byte 00); rewrite the fileset variant-major", path.c_str());
     if (magic[2] != 0x01)
       return sai_set_error(SAI_ERR_ARG, "%s: not a PLINK 1 .bed file (third byte %02X, expected 01)", path.c_str(), magic[2]);
-    const long long want = 3 + static_cast<long long>(idx.n_bim) * static_cast<long long>(idx.row_bytes);
+    const long long want = 3 + static_cast<long long>(idx.rows.n_lines) * static_cast<long long>(idx.row_bytes);
     if (static_cast<long long>(sb.st_size) != want)
       return sai_set_error(SAI_ERR_ARG, "%s: %lld bytes, expected %lld (3 + %lld variants of the .bim x %lld bytes for the %lld samples of the .fam): truncated, or not the .bed of this fileset",
-                           path.c_str(), static_cast<long long>(sb.st_size), want, static_cast<long long>(idx.n_bim),
+                           path.c_str(), static_cast<long long>(sb.st_size), want, static_cast<long long>(idx.rows.n_lines),
                            static_cast<long long>(idx.row_bytes), static_cast<long long>(idx.n_fam));
   }
   *index_out = holder.release();
@@ -361,23 +150,23 @@ int sai_plink_open(const char* prefix, const char* chrom, int64_t start, int64_t
 int sai_plink_index_info(const sai_plink_index* index, int64_t* n_rows, int64_t* n_matched, int64_t* n_anc_entries,
                          int64_t* row_bytes, int64_t* n_fam, int64_t* n_bim, int64_t* first_pos, int64_t* last_pos) {
   if (!index) return sai_set_error(SAI_ERR_ARG, "index is NULL");
-  if (n_rows) *n_rows = static_cast<int64_t>(index->pos.size());
-  if (n_matched) *n_matched = index->n_matched;
+  if (n_rows) *n_rows = static_cast<int64_t>(index->rows.pos.size());
+  if (n_matched) *n_matched = index->rows.n_matched;
   if (n_anc_entries) *n_anc_entries = index->n_anc_entries;
   if (row_bytes) *row_bytes = index->row_bytes;
   if (n_fam) *n_fam = index->n_fam;
-  if (n_bim) *n_bim = index->n_bim;
-  if (first_pos) *first_pos = index->first;
-  if (last_pos) *last_pos = index->last;
+  if (n_bim) *n_bim = index->rows.n_lines;
+  if (first_pos) *first_pos = index->rows.first;
+  if (last_pos) *last_pos = index->rows.last;
   return SAI_OK;
 }
 
 int sai_plink_index_copy(const sai_plink_index* index, int32_t* pos, int64_t* file_row, uint8_t* flip, int32_t* col_of_slot) {
   if (!index) return sai_set_error(SAI_ERR_ARG, "index is NULL");
-  const size_t n = index->pos.size();
-  if (pos && n) memcpy(pos, index->pos.data(), n * sizeof(int32_t));
-  if (file_row && n) memcpy(file_row, index->file_row.data(), n * sizeof(int64_t));
-  if (flip && n) memcpy(flip, index->flip.data(), n);
+  const size_t n = index->rows.pos.size();
+  if (pos && n) memcpy(pos, index->rows.pos.data(), n * sizeof(int32_t));
+  if (file_row && n) memcpy(file_row, index->rows.file_row.data(), n * sizeof(int64_t));
+  if (flip && n) memcpy(flip, index->rows.flip.data(), n);
   if (col_of_slot && !index->col_of_slot.empty()) memcpy(col_of_slot, index->col_of_slot.data(), index->col_of_slot.size() * sizeof(int32_t));
   return SAI_OK;
 }

@@ -56,6 +56,19 @@ def existed_fileset(prefix: Optional[str]) -> Optional[str]:
     return prefix
 
 
+def existed_eigenstrat(prefix: Optional[str]) -> Optional[str]:
+    """The prefix itself (a trailing ``.geno`` is dropped) when PREFIX.geno, PREFIX.snp and PREFIX.ind are
+    regular files (or it is None)."""
+    if prefix is None:
+        return None
+    if prefix.endswith(".geno") and not os.path.isfile(prefix + ".geno"):
+        prefix = prefix[: -len(".geno")]
+    for ext in (".geno", ".snp", ".ind"):
+        if not os.path.isfile(prefix + ext):
+            raise argparse.ArgumentTypeError(f"{prefix}{ext} is not found")
+    return prefix
+
+
 def validate_stat_type(label: str) -> str:
     """A statistic label of the form letter + two digits: ``U05`` (U with x > 0.05), ``Q95`` (Q at the
     0.95 quantile).  Not used by the current commands; kept because the module's interface has it

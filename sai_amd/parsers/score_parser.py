@@ -7,7 +7,7 @@ import argparse
 
 from ..launcher import workers_from_env
 from ..sai import score
-from .argument_validation import existed_file, existed_fileset, positive_int
+from .argument_validation import existed_eigenstrat, existed_file, existed_fileset, positive_int
 
 
 def resolve_workers(args: argparse.Namespace) -> int:
@@ -23,11 +23,16 @@ def resolve_workers(args: argparse.Namespace) -> int:
 
 
 def resolve_input(args: argparse.Namespace) -> str:
-    """Exactly one of ``--vcf`` and ``--bfile``: the path ``score`` takes as its ``vcf_file`` (a fileset is handed
-    over as ``PREFIX.bed``).  Decided here, not by argparse's ``required=True`` -- neither flag is required alone --
-    but reported the same way, as a usage error with status 2."""
-    if (args.vcf is None) == (args.bfile is None):
-        args.score_parser.error("exactly one of the arguments --vcf and --bfile is required")
+    """Exactly one of ``--vcf``, ``--bfile`` and ``--eigenstrat``: the path ``score`` takes as its ``vcf_file`` (a
+    fileset is handed over as ``PREFIX.bed`` / ``PREFIX.geno``).  Decided here, not by argparse's ``required=True``
+    -- no flag is required alone -- but reported the same way, as a usage error with status 2."""
+    given = [flag for flag in (args.vcf, args.bfile, args.eigenstrat) if flag is not None]
+    if len(given) != 1:
+        if args.eigenstrat is None:
+            args.score_parser.error("exactly one of the arguments --vcf and --bfile is required")
+        args.score_parser.error("exactly one of the arguments --vcf, --bfile and --eigenstrat is required")
+    if args.eigenstrat is not None:
+        return args.eigenstrat + ".geno"
     return args.vcf if args.bfile is None else args.bfile + ".bed"
 
 
@@ -54,6 +59,11 @@ def add_score_parser(subparsers) -> None:
                         help="Prefix of a PLINK 1 binary fileset (PREFIX.bed + PREFIX.bim + PREFIX.fam, variant-major) to "
                         "read instead of a VCF; A2 is taken as the reference allele and A1 as the alternative one. "
                         "Exactly one of --vcf and --bfile is required.")  # fmt: skip
+    # ... or as an EIGENSOFT fileset: text EIGENSTRAT, PACKEDANCESTRYMAP or its transposed form, told apart by content
+    parser.add_argument("--eigenstrat", type=existed_eigenstrat, default=None, metavar="PREFIX",
+                        help="Prefix of an EIGENSOFT fileset (PREFIX.geno + PREFIX.snp + PREFIX.ind; text, packed or "
+                        "transposed packed) to read instead of a VCF or a PLINK fileset; the first allele of the .snp is "
+                        "taken as the reference allele and the second as the alternative one.")  # fmt: skip
     parser.add_argument("--chr-name", dest="chr_name", type=str, required=True,
                         help="Chromosome name to analyze from the VCF file.")  # fmt: skip
     parser.add_argument("--win-len", dest="win_len", type=positive_int, default=50000,

@@ -82,8 +82,9 @@ def _reads_in_one_pass(vcf_file: str) -> bool:
     the file, chunk_generator.py:64-82) are found WHILE the one streaming read fills HBM -- the scan was 10
     of the 24 ms of a 482 MB file.  Compressed files keep the order scan, then read: an indexed one scans
     two records, and the scan of an unindexed bgzip file is itself a pass of the GPU reader.  A PLINK fileset is
-    scanned from its ``.bim`` alone, which the read would index a second time: scan, then read."""
-    from .utils.plink import is_fileset
+    scanned from its ``.bim`` alone (an EIGENSOFT one from its ``.snp``), which the read would index a second time:
+    scan, then read."""
+    from .utils.filesets import is_fileset
 
     if is_fileset(vcf_file):
         return False
@@ -148,18 +149,17 @@ def chunks_for_memory(vcf_file: str) -> int:
     The estimate is the file's: a genotype is about four bytes of VCF text ("0|1" + tab; bgzip shrinks genotype
     text about twelvefold), of which one int8 dosage stays resident -- besides the reader's staging and the tiled
     copy per population, hence a budget of a quarter of the free HBM.  ``SAI_AMD_HBM_BUDGET_BYTES`` overrides it.
-    A PLINK ``.bed`` holds four genotypes per byte: 4 x its size stays resident."""
-    from .utils.plink import fileset_prefix
+    A PLINK ``.bed`` and a packed ``.geno`` hold four genotypes per byte: 4 x their size stays resident; a text
+    ``.geno`` holds one: 1 x."""
+    from .utils.filesets import resident_bytes
 
-    prefix = fileset_prefix(vcf_file)
     try:
-        size = os.path.getsize(vcf_file if prefix is None else prefix + ".bed")
+        resident = resident_bytes(vcf_file)
+        if resident is None:
+            size = os.path.getsize(vcf_file)
+            resident = size * 3 if str(vcf_file).endswith((".gz", ".bgz")) else size // 4
     except OSError:
         return 1
-    if prefix is not None:
-        resident = size * 4
-    else:
-        resident = size * 3 if str(vcf_file).endswith((".gz", ".bgz")) else size // 4
     raw = os.environ.get("SAI_AMD_HBM_BUDGET_BYTES", "")
     if raw:
         budget = int(raw)
@@ -190,11 +190,9 @@ def _score_over_ranks(vcf_file, chr_name, win_len, win_step, anc_allele_file, ou
 
 
 def _score_cli_arguments(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config, num_workers) -> list:
-    from .utils.plink import fileset_prefix
+    from .utils.filesets import cli_source
 
-    prefix = fileset_prefix(vcf_file)
-    source = ["--vcf", vcf_file] if prefix is None else ["--bfile", prefix]
-    argv = ["score", *source, "--chr-name", chr_name, "--win-len", win_len, "--win-step", win_step,
+    argv = ["score", *cli_source(vcf_file), "--chr-name", chr_name, "--win-len", win_len, "--win-step", win_step,
             "--output", output_file, "--config", config, "--num-workers", num_workers]  # fmt: skip
     if anc_allele_file is not None:
         argv += ["--anc-alleles", anc_allele_file]
@@ -255,7 +253,7 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
         # the readers' staging (about 650 MB of HBM + 125 MB pinned for a large bgzip file) is kept for the
         # next call by default -- allocating and page-locking it costs more than a small `score`
         from .engine import Engine
-        from .utils.plink import release_buffers
+        from .utils.filesets import release_buffers
 
         Engine.get().release_ingest_buffers()
         release_buffers(Engine.get())

@@ -1,6 +1,7 @@
-"""The steps the ingest readers share (``native_vcf``, ``device_vcf``, ``plink``): the region / sample
-arguments of the C ABI, its errors as ValueError, the staging kept on the engine, and -- ``Records`` --
-what the two GPU-tokenising VCF routes do with the record lines of a batch."""
+"""The steps the ingest readers share (``native_vcf``, ``device_vcf``, ``plink``, ``eigenstrat``): the region /
+sample arguments of the C ABI, its errors as ValueError, the staging kept on the engine, the batches and the
+``pread`` of fixed-length rows (the two fileset readers), and -- ``Records`` -- what the two GPU-tokenising VCF
+routes do with the record lines of a batch."""
 
 from __future__ import annotations
 
@@ -55,6 +56,90 @@ def pair(n: int, dtype=None, device=None) -> list:
 
     bufs = [torch.empty((n,), dtype=dtype or torch.uint8, device=device) for _ in range(2)]
     return bufs if device is not None else [t.pin_memory() for t in bufs]
+
+
+def row_batches(file_row, row_bytes: int, data_offset: int, cap: int, read_through: int, data_path: str, index_path: str):
+    """Cut the selected rows ``file_row`` (ascending 0-based rows of ``row_bytes`` bytes that start at
+    ``data_offset`` of the file) into batches of at most ``cap`` bytes of whole rows.  Selected rows that are close
+    in the file are read as one range, the rows between them included when they come to at most ``read_through``
+    bytes (a ``pread`` per row would cost more than their bytes); the ranges of a batch lie back to back in its
+    buffer.  Yields ``(k0, k1, row_in_batch int32 [k1 - k0], n_batch_rows, reads)`` with ``reads`` = [(buffer
+    offset, file offset, bytes)]."""
+    rb, n_rows = row_bytes, len(file_row)
+    if n_rows == 0 or rb == 0:
+        return
+    per_batch = cap // rb
+    if per_batch < 1:
+        raise ValueError(f"SAI_AMD_INGEST_BUFFER of {cap} bytes is smaller than one row of {data_path} ({rb} bytes)")
+    rows = file_row
+    new_range = np.empty(n_rows, dtype=bool)
+    new_range[0] = True
+    new_range[1:] = np.diff(rows) > 1 + read_through // rb
+    if n_rows > 1 and bool((np.diff(rows) <= 0).any()):
+        raise ValueError(f"{index_path}: the index is not in file order")
+    starts = np.flatnonzero(new_range)
+    range_first = rows[starts]  # first file row of every range
+    range_last = rows[np.append(starts[1:] - 1, n_rows - 1)]
+    range_base = np.concatenate(([0], np.cumsum(range_last - range_first + 1)))  # ... its place in the stream of all ranges
+    range_of = np.cumsum(new_range) - 1
+    stream_row = rows - range_first[range_of] + range_base[range_of]  # ascending
+    total = int(range_base[-1])
+    for lo in range(0, total, per_batch):
+        hi = min(lo + per_batch, total)
+        k0, k1 = (int(x) for x in np.searchsorted(stream_row, (lo, hi)))
+        reads = []
+        j = int(np.searchsorted(range_base, lo, side="right")) - 1
+        at = lo
+        while at < hi:
+            stop = min(hi, int(range_base[j + 1]))
+            reads.append(((at - lo) * rb, data_offset + (int(range_first[j]) + at - int(range_base[j])) * rb, (stop - at) * rb))
+            at = stop
+            j += 1
+        yield k0, k1, (stream_row[k0:k1] - lo).astype(np.int32), hi - lo, reads
+
+
+_PREAD_PIECE = 4 << 20  # a batch is read by several threads in pieces of this size
+_pool = None
+
+
+def _read_pool():
+    from concurrent.futures import ThreadPoolExecutor
+
+    global _pool
+    if _pool is None or getattr(_pool, "_owner", None) != os.getpid():  # threads do not survive a fork
+        _pool = ThreadPoolExecutor(max(1, min(default_threads(), 8)), thread_name_prefix="sai-fileset-read")
+        _pool._owner = os.getpid()
+    return _pool
+
+
+def pread_into(fd: int, view: memoryview, reads, path: str) -> None:
+    """Fill ``view`` from the file: ``reads`` = [(buffer offset, file offset, bytes)], large ones in pieces on
+    several threads (``preadv`` releases the GIL; one thread copies the page cache at a fraction of what PCIe takes)."""
+    pieces = []
+    for at, off, n in reads:
+        for d in range(0, n, _PREAD_PIECE):
+            pieces.append((at + d, off + d, min(_PREAD_PIECE, n - d)))
+
+    def one(piece):
+        at, off, n = piece
+        done = 0
+        while done < n:
+            got = os.preadv(fd, [view[at + done : at + n]], off + done)
+            if got <= 0:
+                raise ValueError(f"{path}: read error or unexpected end of file at byte {off + done}")
+            done += got
+
+    if len(pieces) > 1:
+        pool = _read_pool()
+        workers = pool._max_workers
+        if len(pieces) > 2 * workers:  # many small reads (one per individual of a transposed .geno): a share per thread, not a task each
+            share = -(-len(pieces) // workers)
+            list(pool.map(lambda lo: [one(piece) for piece in pieces[lo : lo + share]], range(0, len(pieces), share)))
+        else:
+            list(pool.map(one, pieces))
+    else:
+        for piece in pieces:
+            one(piece)
 
 
 class Records:

@@ -1,0 +1,62 @@
+"""Which reader serves a path: the one place the callers (``read_data``, ``native_vcf.scan_first_last``,
+``sai.score``) ask whether ``vcf_file`` names a genotype fileset instead of a VCF.
+
+``reader_for(path)`` gives the reader module (``plink`` or ``eigenstrat``: both have ``fileset_prefix``,
+``scan_first_last``, ``load_dosage``, ``load_dosage_device`` and ``release_buffers``) or None for anything else,
+which is then read as a VCF.  Detection is by content; a bare prefix that has both kinds of files is PLINK."""
+
+from __future__ import annotations
+
+import os
+from typing import Optional
+
+from . import eigenstrat, plink
+
+READERS = (plink, eigenstrat)
+# per reader: the flag of `sai score` that takes its prefix, the file whose size tells the genotype count, what it is called
+_FLAG = {plink: "--bfile", eigenstrat: "--eigenstrat"}
+_DATA = {plink: ".bed", eigenstrat: ".geno"}
+_NAME = {plink: "a PLINK fileset", eigenstrat: "an EIGENSTRAT fileset"}
+
+
+def reader_for(path):
+    for reader in READERS:
+        if reader.fileset_prefix(path) is not None:
+            return reader
+    return None
+
+
+def is_fileset(path) -> bool:
+    return reader_for(path) is not None
+
+
+def name_of(path) -> Optional[str]:
+    """"a PLINK fileset" / "an EIGENSTRAT fileset", else None."""
+    reader = reader_for(path)
+    return None if reader is None else _NAME[reader]
+
+
+def cli_source(path) -> list:
+    """The input arguments of ``sai score`` that name ``path``: ``--vcf``, ``--bfile`` or ``--eigenstrat``."""
+    reader = reader_for(path)
+    return ["--vcf", path] if reader is None else [_FLAG[reader], reader.fileset_prefix(path)]
+
+
+def resident_bytes(path) -> Optional[int]:
+    """The int8 genotype bytes that stay resident for a fileset (None for anything else): a 2-bit file holds four
+    genotypes per byte, a text ``.geno`` one."""
+    reader = reader_for(path)
+    if reader is None:
+        return None
+    data = reader.fileset_prefix(path) + _DATA[reader]
+    size = os.path.getsize(data)
+    if reader is eigenstrat:
+        with open(data, "rb") as f:
+            if not f.read(6).lstrip(b"T").startswith(b"GENO"):
+                return size
+    return size * 4
+
+
+def release_buffers(eng) -> None:
+    for reader in READERS:
+        reader.release_buffers(eng)

@@ -20,11 +20,13 @@ def scan_first_last(vcf_file: str, chr_name: str) -> tuple[Optional[int], Option
     and its last one) whatever the size of the file -- every rank of a sharded run asks this question.
     Otherwise a bgzip file is scanned with the GPU-inflate pass when a GPU is there (the host would
     inflate the whole file for it: 53 ms against 12 for 480 MB of text); everything else, and every
-    machine without a GPU, takes the host scan.  A PLINK 1 fileset answers from its ``.bim``."""
-    from . import plink
+    machine without a GPU, takes the host scan.  A PLINK 1 fileset answers from its ``.bim``,
+    an EIGENSOFT one from its ``.snp``."""
+    from .filesets import reader_for
 
-    if plink.is_fileset(vcf_file):
-        return plink.scan_first_last(vcf_file, chr_name)
+    reader = reader_for(vcf_file)
+    if reader is not None:
+        return reader.scan_first_last(vcf_file, chr_name)
     if str(vcf_file).endswith((".gz", ".bgz")) and os.environ.get("SAI_AMD_INGEST") != "host" and not _index_usable(vcf_file):
         got = _scan_on_device(vcf_file, chr_name)
         if got is not None:

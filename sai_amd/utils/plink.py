@@ -17,19 +17,17 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from concurrent.futures import ThreadPoolExecutor
 from typing import Optional, Sequence
 
 import numpy as np
 
 from .. import _ffi, _ffi_plink
-from ._ingest import check_io, default_threads, pair, region_args, staging
+from ._ingest import check_io, default_threads, pair, pread_into, region_args, row_batches, staging
 
 BUFFER_BYTES = 32 << 20  # as the VCF route (device_vcf.BUFFER_BYTES); SAI_AMD_INGEST_BUFFER overrides it
 _MAGIC = b"\x6c\x1b"
 _EXTENSIONS = (".bed", ".bim", ".fam")
 _READ_THROUGH_BYTES = 64 << 10  # unselected rows between two selected ones are read along up to this many bytes
-_PREAD_PIECE = 4 << 20  # a batch is read by several threads in pieces of this size
 
 
 def fileset_prefix(path) -> Optional[str]:
@@ -109,37 +107,7 @@ class _Index:
         would cost more than their bytes); the ranges of a batch lie back to back in its buffer.  Yields
         ``(k0, k1, row_in_batch int32 [k1 - k0], n_batch_rows, reads)`` with ``reads`` = [(buffer offset,
         file offset, bytes)]."""
-        rb = self.row_bytes
-        if self.n_rows == 0 or rb == 0:
-            return
-        per_batch = cap // rb
-        if per_batch < 1:
-            raise ValueError(f"SAI_AMD_INGEST_BUFFER of {cap} bytes is smaller than one row of {self.prefix}.bed ({rb} bytes)")
-        rows = self.file_row
-        new_range = np.empty(self.n_rows, dtype=bool)
-        new_range[0] = True
-        new_range[1:] = np.diff(rows) > 1 + _READ_THROUGH_BYTES // rb
-        if self.n_rows > 1 and bool((np.diff(rows) <= 0).any()):
-            raise ValueError(f"{self.prefix}.bim: the index is not in file order")
-        starts = np.flatnonzero(new_range)
-        range_first = rows[starts]  # first file row of every range
-        range_last = rows[np.append(starts[1:] - 1, self.n_rows - 1)]
-        range_base = np.concatenate(([0], np.cumsum(range_last - range_first + 1)))  # ... its place in the stream of all ranges
-        range_of = np.cumsum(new_range) - 1
-        stream_row = rows - range_first[range_of] + range_base[range_of]  # ascending
-        total = int(range_base[-1])
-        for lo in range(0, total, per_batch):
-            hi = min(lo + per_batch, total)
-            k0, k1 = (int(x) for x in np.searchsorted(stream_row, (lo, hi)))
-            reads = []
-            j = int(np.searchsorted(range_base, lo, side="right")) - 1
-            at = lo
-            while at < hi:
-                stop = min(hi, int(range_base[j + 1]))
-                reads.append(((at - lo) * rb, 3 + (int(range_first[j]) + at - int(range_base[j])) * rb, (stop - at) * rb))
-                at = stop
-                j += 1
-            yield k0, k1, (stream_row[k0:k1] - lo).astype(np.int32), hi - lo, reads
+        return row_batches(self.file_row, self.row_bytes, 3, cap, _READ_THROUGH_BYTES, f"{self.prefix}.bed", f"{self.prefix}.bim")
 
     def raise_flagged(self, status: np.ndarray, row0: int = 0) -> None:
         """The first flagged row of ``status`` (rows ``row0 ..`` of the index) as the reader's ValueError."""
@@ -172,41 +140,6 @@ def _variant_id(prefix: str, file_row: int) -> str:
     return f"#{file_row + 1}"
 
 
-_pool = None
-
-
-def _read_pool() -> ThreadPoolExecutor:
-    global _pool
-    if _pool is None or getattr(_pool, "_owner", None) != os.getpid():  # threads do not survive a fork
-        _pool = ThreadPoolExecutor(max(1, min(default_threads(), 8)), thread_name_prefix="sai-plink-read")
-        _pool._owner = os.getpid()
-    return _pool
-
-
-def _pread_into(fd: int, view: memoryview, reads, path: str) -> None:
-    """Fill ``view`` from the file: ``reads`` = [(buffer offset, file offset, bytes)], large ones in pieces on
-    several threads (``preadv`` releases the GIL; one thread copies the page cache at a fraction of what PCIe takes)."""
-    pieces = []
-    for at, off, n in reads:
-        for d in range(0, n, _PREAD_PIECE):
-            pieces.append((at + d, off + d, min(_PREAD_PIECE, n - d)))
-
-    def one(piece):
-        at, off, n = piece
-        done = 0
-        while done < n:
-            got = os.preadv(fd, [view[at + done : at + n]], off + done)
-            if got <= 0:
-                raise ValueError(f"{path}: read error or unexpected end of file at byte {off + done}")
-            done += got
-
-    if len(pieces) > 1:
-        list(_read_pool().map(one, pieces))
-    else:
-        for piece in pieces:
-            one(piece)
-
-
 def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[int], start: Optional[int] = None,
                 end: Optional[int] = None, anc_allele_file: Optional[str] = None, n_threads: Optional[int] = None,
                 buffer_bytes: Optional[int] = None):  # fmt: skip
@@ -229,7 +162,7 @@ def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[
             nbytes = n_batch_rows * idx.row_bytes
             if buf is None or buf.size < nbytes:
                 buf = np.empty(nbytes, dtype=np.uint8)
-            _pread_into(fd, memoryview(buf), reads, idx.prefix + ".bed")
+            pread_into(fd, memoryview(buf), reads, idx.prefix + ".bed")
             if k1 == k0:
                 continue
             check_io(lib, lib.sai_plink_decode_host(
@@ -302,7 +235,7 @@ def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidie
             if copied[b] is not None:
                 copied[b].synchronize()  # the copy two batches back has left this pinned buffer
             t1 = time.perf_counter()
-            _pread_into(fd, memoryview(pinned[b].numpy()), reads, idx.prefix + ".bed")
+            pread_into(fd, memoryview(pinned[b].numpy()), reads, idx.prefix + ".bed")
             if trace is not None:
                 trace["file_read"] = trace.get("file_read", 0.0) + time.perf_counter() - t1
                 trace["bed_bytes"] += nbytes

@@ -42,14 +42,15 @@ def read_data(
     ``filter_missing`` = drop the sites where a sample of the population has a missing allele.  Blocks
     carry REF / ALT.  All options off and unphased is the ``score`` path's request: it goes to the native
     tokenizer (``read_dosage_data``: int8 dosages, REF / ALT not kept)."""
-    from .plink import is_fileset
+    from .filesets import name_of
 
     if not (is_phased or filter_ref or filter_tgt or filter_src or filter_out or filter_missing):
         return read_dosage_data(vcf_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
                                 anc_allele_file, start, end, engine)  # fmt: skip
-    if is_fileset(vcf_file):
+    kind = name_of(vcf_file)
+    if kind is not None:
         # a fileset has neither phase nor REF / ALT columns to hand out: only the dosage request is served from it
-        raise ValueError(f"{vcf_file}: a PLINK fileset is read as unphased dosages only "
+        raise ValueError(f"{vcf_file}: {kind} is read as unphased dosages only "
                          "(is_phased=False and every filter_* option off); convert it to VCF for the other options")  # fmt: skip
     from .geno import load_population_data
 
@@ -198,14 +199,16 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
     ``(results, pos_dev)``: ``results`` as ``read_data`` gives it, except that every ``GT`` is a
     ``TiledPop``; ``pos_dev`` = the int32 device copy of the positions (None without data).  A PLINK 1
     fileset takes the same way with its own reader (``plink.load_dosage_device``: ``.bed`` rows over PCIe,
-    decoded on the GPU); there a slot is a (sample, ploidy) request, so one pass always serves all."""
+    decoded on the GPU), and so does an EIGENSOFT one (``eigenstrat.load_dosage_device``); there a slot is a
+    (sample, ploidy) request, so one pass always serves all."""
     import torch
 
-    from . import plink
+    from .filesets import reader_for
 
-    fileset = plink.is_fileset(vcf_file)
+    reader = reader_for(vcf_file)
+    fileset = reader is not None
     if fileset:
-        load_dosage_device = plink.load_dosage_device
+        load_dosage_device = reader.load_dosage_device
     else:
         from .device_vcf import load_dosage_device
 
@@ -259,12 +262,13 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
 
 def _load_native(vcf_file, chr_name, names, ploidy, start, end, anc_allele_file):
     """libsaihip's multithreaded tokenizer (sai_amd/csrc/vcf_ingest.cpp), or its fileset reader
-    (sai_amd/csrc/plink) when the path names a PLINK 1 fileset."""
-    from . import plink
+    (sai_amd/csrc/plink, sai_amd/csrc/eigenstrat) when the path names a PLINK 1 or an EIGENSOFT fileset."""
+    from .filesets import reader_for
     from .native_vcf import load_dosage
 
-    if plink.is_fileset(vcf_file):
-        return plink.load_dosage(vcf_file, chr_name, names, [ploidy] * len(names), start, end, anc_allele_file)
+    reader = reader_for(vcf_file)
+    if reader is not None:
+        return reader.load_dosage(vcf_file, chr_name, names, [ploidy] * len(names), start, end, anc_allele_file)
     if not os.path.exists(vcf_file):
         raise ValueError(f"cannot open VCF {vcf_file}")
     return load_dosage(vcf_file, chr_name, names, [ploidy] * len(names), start, end, anc_allele_file)
