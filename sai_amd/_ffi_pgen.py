@@ -1,0 +1,66 @@
+"""ctypes binding of the PLINK 2 fileset entry points of libsaihip.so (include/saihip_pgen.h).
+
+They live in the same shared library as the entry points of ``_ffi`` (and their host part in the
+sanitizer build of the host units), but in a header and a table of their own, with their own version
+number: ``load()`` / ``load_host()`` take the handle ``_ffi`` returns and declare the prototypes below
+on it.  A library without them is an error, as everywhere in this package.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _ffi
+
+SAI_PGEN_ABI_VERSION = 1
+SAI_PGEN_STATUS_BAD_INDEX = 0x7FFFFFFF
+SAI_PGEN_STATUS_BAD_RECORD = 0x7FFFFFFE
+
+_p, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
+
+# name -> (restype, argtypes): the names include/saihip_pgen.h declares
+SIGNATURES = {
+    "sai_pgen_abi_version": (C.c_int, []),
+    "sai_pgen_scan": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sai_pgen_open": (
+        C.c_int,
+        [C.c_char_p, C.c_char_p, _i64, _i64, _i32, C.POINTER(C.c_char_p), C.POINTER(_i32), C.c_char_p, _i32, C.POINTER(_p)],
+    ),
+    "sai_pgen_index_info": (C.c_int, [_p] + [C.POINTER(_i64)] * 8),
+    "sai_pgen_index_copy": (C.c_int, [_p, _p, _p, _p, _p, _p, _p]),
+    "sai_pgen_index_close": (C.c_int, [_p]),
+    "sai_pgen_decode_host": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _i32]),
+    "sai_pgen_decode": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _i32, _i32, _p, _i32, _p, _i32, _p, _i64, _p, _p]),
+}
+
+# entry points that never touch the GPU (pgen_index.cpp)
+HOST_SYMBOLS = tuple(n for n in SIGNATURES if n != "sai_pgen_decode")
+
+
+def _attach(lib: C.CDLL, names) -> C.CDLL:
+    if getattr(lib, "_sai_pgen_attached", None) == tuple(names):
+        return lib
+    for name in names:
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise RuntimeError(f"{name} is missing from libsaihip: the library was built without sai_amd/csrc/pgen "
+                               "(rebuild it: `python -c 'import __graft_entry__ as g; g.build()'`)") from None  # fmt: skip
+        fn.restype, fn.argtypes = SIGNATURES[name]
+    if lib.sai_pgen_abi_version() != SAI_PGEN_ABI_VERSION:
+        raise RuntimeError(f"libsaihip: PGEN ABI {lib.sai_pgen_abi_version()} != expected {SAI_PGEN_ABI_VERSION}")
+    lib._sai_pgen_attached = tuple(names)
+    return lib
+
+
+def load() -> C.CDLL:
+    """``_ffi.load()`` with every prototype of saihip_pgen.h declared."""
+    return _attach(_ffi.load(), tuple(SIGNATURES))
+
+
+def load_host() -> C.CDLL:
+    """``_ffi.load_host()`` with the host-only prototypes declared (the sanitizer build has no kernel)."""
+    lib = _ffi.load_host()
+    if lib is _ffi._lib:
+        return load()
+    return _attach(lib, HOST_SYMBOLS)

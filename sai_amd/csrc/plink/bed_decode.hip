@@ -22,6 +22,7 @@
 
 #include "../common.hpp"
 #include "plink_codes.hpp"
+#include "recode16.hpp"
 #include "saihip_plink.h"
 
 namespace {
@@ -121,16 +122,7 @@ __global__ __launch_bounds__(kDecodeBlock) void bed_decode_kernel(DecodeArgs a) 
         const uint32_t het = (codes >> 1) & ~codes & 0x55555555u;  // bit 2k set: code k is 10
         if (het && r.ok) atomicMax(a.status + row, a.n_slots - (slot + (__builtin_ctz(het) >> 1)));
       }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const uint32_t code = (codes >> (2 * (4 * j + k))) & 3u;
-          w |= ((lut >> (8 * code)) & 0xFFu) << (8 * k);
-        }
-        word[j] = r.ok ? w : 0u;
-      }
+      SAI_RECODE16(codes, lut, r.ok, word)
       *reinterpret_cast<u32x4*>(a.out + e0) = word;
       continue;
     }

@@ -74,6 +74,7 @@ struct VariantLayout {
   int min_cols;         // a record line with fewer columns is refused; the allele columns may lie beyond it (then optional)
   bool hash_comments;   // lines whose first non-blank character is '#' are skipped
   bool strict_pos;      // a position that is not a plain non-negative integer is refused
+  bool mark_multi = false;  // the first selected row whose ALT column holds a comma is reported (VariantRows::first_multi)
 };
 
 // The rows a variant pass selects, and what it learns on the way.
@@ -84,6 +85,7 @@ struct VariantRows {
   int64_t n_matched = 0;
   int64_t n_lines = 0;            // record lines of the whole file
   int64_t first = -1, last = -1;  // the first contiguous run of the chromosome, whole file
+  int64_t first_multi = -1;       // file_row of the first selected row with several ALT alleles (VariantLayout::mark_multi)
 };
 
 enum VariantLineError { kLineFine = 0, kLineShort = 1, kLineBadPos = 2, kLineNoAlleles = 3 };
@@ -99,6 +101,7 @@ struct VariantPiece {
   int64_t bad_line = -1;  // the first refused line (piece-relative) ...
   VariantLineError bad_why = kLineFine;  // ... and why
   bool failed = false;    // out of memory
+  int64_t multi_line = -1;  // the first selected line (piece-relative) with a comma in ALT
 };
 
 constexpr int kMaxVariantCols = 6;
@@ -153,6 +156,7 @@ inline void variant_piece(const char* p, const char* end, const VariantLayout& l
     out.pos.push_back(static_cast<int32_t>(pos));
     out.row.push_back(line);
     out.flip.push_back(d == kFlip ? 1 : 0);
+    if (lay.mark_multi && out.multi_line < 0 && found > lay.alt_col && memchr(tok[lay.alt_col], ',', len[lay.alt_col])) out.multi_line = line;
   }
 }
 
@@ -212,6 +216,7 @@ inline int variant_pass(const std::string& path, const VariantLayout& lay, const
     idx.pos.insert(idx.pos.end(), pc.pos.begin(), pc.pos.end());
     for (int64_t r : pc.row) idx.file_row.push_back(line0 + r);
     idx.flip.insert(idx.flip.end(), pc.flip.begin(), pc.flip.end());
+    if (idx.first_multi < 0 && pc.multi_line >= 0) idx.first_multi = line0 + pc.multi_line;
     line0 += pc.n_lines;
     if (run_over) continue;
     if (idx.first < 0) {

@@ -69,6 +69,21 @@ def existed_eigenstrat(prefix: Optional[str]) -> Optional[str]:
     return prefix
 
 
+def existed_pfile(prefix: Optional[str]) -> Optional[str]:
+    """The prefix itself (a trailing ``.pgen`` is dropped) when PREFIX.pgen, PREFIX.pvar and PREFIX.psam are
+    regular files (or it is None)."""
+    if prefix is None:
+        return None
+    if prefix.endswith(".pgen") and not os.path.isfile(prefix + ".pgen"):
+        prefix = prefix[: -len(".pgen")]
+    for ext in (".pgen", ".pvar", ".psam"):
+        if not os.path.isfile(prefix + ext):
+            if ext == ".pvar" and os.path.isfile(prefix + ".pvar.zst"):
+                raise argparse.ArgumentTypeError(f"{prefix}.pvar is not found, but {prefix}.pvar.zst is: decompress it first (zstd -d)")
+            raise argparse.ArgumentTypeError(f"{prefix}{ext} is not found")
+    return prefix
+
+
 def validate_stat_type(label: str) -> str:
     """A statistic label of the form letter + two digits: ``U05`` (U with x > 0.05), ``Q95`` (Q at the
     0.95 quantile).  Not used by the current commands; kept because the module's interface has it

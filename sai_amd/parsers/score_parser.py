@@ -7,7 +7,7 @@ import argparse
 
 from ..launcher import workers_from_env
 from ..sai import score
-from .argument_validation import existed_eigenstrat, existed_file, existed_fileset, positive_int
+from .argument_validation import existed_eigenstrat, existed_file, existed_fileset, existed_pfile, positive_int
 
 
 def resolve_workers(args: argparse.Namespace) -> int:
@@ -23,14 +23,18 @@ def resolve_workers(args: argparse.Namespace) -> int:
 
 
 def resolve_input(args: argparse.Namespace) -> str:
-    """Exactly one of ``--vcf``, ``--bfile`` and ``--eigenstrat``: the path ``score`` takes as its ``vcf_file`` (a
-    fileset is handed over as ``PREFIX.bed`` / ``PREFIX.geno``).  Decided here, not by argparse's ``required=True``
+    """Exactly one of ``--vcf``, ``--bfile``, ``--eigenstrat`` and ``--pfile``: the path ``score`` takes as its
+    ``vcf_file`` (a fileset is handed over as ``PREFIX.bed`` / ``PREFIX.geno`` / ``PREFIX.pgen``).  Decided here, not by argparse's ``required=True``
     -- no flag is required alone -- but reported the same way, as a usage error with status 2."""
-    given = [flag for flag in (args.vcf, args.bfile, args.eigenstrat) if flag is not None]
+    given = [flag for flag in (args.vcf, args.bfile, args.eigenstrat, args.pfile) if flag is not None]
     if len(given) != 1:
+        if args.pfile is not None:
+            args.score_parser.error("exactly one of the arguments --vcf, --bfile, --eigenstrat and --pfile is required")
         if args.eigenstrat is None:
             args.score_parser.error("exactly one of the arguments --vcf and --bfile is required")
         args.score_parser.error("exactly one of the arguments --vcf, --bfile and --eigenstrat is required")
+    if args.pfile is not None:
+        return args.pfile + ".pgen"
     if args.eigenstrat is not None:
         return args.eigenstrat + ".geno"
     return args.vcf if args.bfile is None else args.bfile + ".bed"
@@ -64,6 +68,10 @@ def add_score_parser(subparsers) -> None:
                         help="Prefix of an EIGENSOFT fileset (PREFIX.geno + PREFIX.snp + PREFIX.ind; text, packed or "
                         "transposed packed) to read instead of a VCF or a PLINK fileset; the first allele of the .snp is "
                         "taken as the reference allele and the second as the alternative one.")  # fmt: skip
+    # ... or as a PLINK 2 fileset, what plink2 writes by default: its compressed records are expanded on the GPU
+    parser.add_argument("--pfile", type=existed_pfile, default=None, metavar="PREFIX",
+                        help="Prefix of a PLINK 2 binary fileset (PREFIX.pgen + PREFIX.pvar + PREFIX.psam) to read instead of "
+                        "a VCF or another fileset; REF and ALT are what the .pvar names, hard calls are read.")  # fmt: skip
     parser.add_argument("--chr-name", dest="chr_name", type=str, required=True,
                         help="Chromosome name to analyze from the VCF file.")  # fmt: skip
     parser.add_argument("--win-len", dest="win_len", type=positive_int, default=50000,

@@ -1,6 +1,7 @@
-"""The steps the ingest readers share (``native_vcf``, ``device_vcf``, ``plink``, ``eigenstrat``): the region /
+"""The steps the ingest readers share (``native_vcf``, ``device_vcf``, ``plink``, ``eigenstrat``, ``pgen``): the region /
 sample arguments of the C ABI, its errors as ValueError, the staging kept on the engine, the batches and the
-``pread`` of fixed-length rows (the two fileset readers), and -- ``Records`` -- what the two GPU-tokenising VCF
+``pread`` of fixed-length rows (the PLINK 1 and EIGENSOFT readers) and of variable-length records (the PLINK 2
+reader), and -- ``Records`` -- what the two GPU-tokenising VCF
 routes do with the record lines of a batch."""
 
 from __future__ import annotations
@@ -96,6 +97,68 @@ def row_batches(file_row, row_bytes: int, data_offset: int, cap: int, read_throu
             at = stop
             j += 1
         yield k0, k1, (stream_row[k0:k1] - lo).astype(np.int32), hi - lo, reads
+
+
+def span_batches(rec, base, cap: int, read_through: int, data_path: str):
+    """``row_batches`` for records of variable length.  ``rec`` = int64 [n][3], the (file offset, length, type) of
+    every selected row's record in file order; ``base`` = the same of the record it differs from, or -1.  The wanted
+    records -- rows and bases -- are laid out as one stream in file order, records between two wanted ones read along
+    when they come to at most ``read_through`` bytes; a batch is a piece of that stream that ends behind a row, at
+    most ``cap`` bytes.  A base that lies before the piece can only be the base of the batch's first row (every
+    record between a base and its row differs from the same base): it is read to the front of the buffer, even when
+    its own row went out with the previous batch.  Yields ``(k0, k1, rec [k1 - k0][3], base [k1 - k0][3], n_bytes,
+    reads)``, the offsets of the two tables counted from the start of the buffer, ``reads`` = [(buffer offset, file
+    offset, bytes)]."""
+    n_rows = len(rec)
+    if n_rows == 0:
+        return
+    rec_off, rec_len = rec[:, 0], rec[:, 1]
+    if n_rows > 1 and bool((np.diff(rec_off) <= 0).any()):
+        raise ValueError(f"{data_path}: the index is not in file order")
+    has_base = base[:, 0] >= 0
+    if bool((base[has_base, 0] >= rec_off[has_base]).any()):
+        raise ValueError(f"{data_path}: a record's base does not lie before it")
+    offs, where = np.unique(np.concatenate((rec_off, base[has_base, 0])), return_index=True)
+    lens = np.concatenate((rec_len, base[has_base, 1]))[where]
+    gap = offs[1:] - (offs[:-1] + lens[:-1])
+    if bool((gap < 0).any()):
+        raise ValueError(f"{data_path}: records overlap")
+    new_range = np.ones(len(offs), dtype=bool)
+    new_range[1:] = gap > read_through
+    skipped = np.concatenate(([0], np.cumsum(np.where(new_range[1:], gap, 0))))
+    at_stream = offs - offs[0] - skipped  # where every wanted record starts in the stream
+    starts = np.flatnonzero(new_range)
+    range_stream, range_file = at_stream[starts], offs[starts]
+    range_end = np.append(range_stream[1:], at_stream[-1] + lens[-1])
+    rec_at = at_stream[np.searchsorted(offs, rec_off)]
+    rec_end = rec_at + rec_len
+    base_at = np.where(has_base, at_stream[np.searchsorted(offs, np.where(has_base, base[:, 0], offs[0]))], -1)
+    k0 = 0
+    while k0 < n_rows:
+        lo = int(rec_at[k0])
+        front = int(base[k0, 1]) if has_base[k0] else 0  # the first row's base, read on its own
+        k1 = int(np.searchsorted(rec_end, lo + cap - front, side="right"))
+        if k1 <= k0:
+            raise ValueError(f"SAI_AMD_INGEST_BUFFER of {cap} bytes is smaller than one record of {data_path} "
+                             f"({int(rec_len[k0])} bytes{f' and its base of {front}' if front else ''})")  # fmt: skip
+        hi = int(rec_end[k1 - 1])
+        reads = [(0, int(base[k0, 0]), front)] if front else []
+        j = int(np.searchsorted(range_stream, lo, side="right")) - 1
+        at = lo
+        while at < hi:
+            stop = min(hi, int(range_end[j]))
+            reads.append((front + at - lo, int(range_file[j]) + at - int(range_stream[j]), stop - at))
+            at = stop
+            j += 1
+        rows, bases = rec[k0:k1].copy(), base[k0:k1].copy()
+        rows[:, 0] = rec_at[k0:k1] - lo + front
+        inside = base_at[k0:k1] >= lo
+        before = has_base[k0:k1] & ~inside
+        if bool((base[k0:k1, 0][before] != base[k0, 0]).any()):
+            raise ValueError(f"{data_path}: rows of one batch differ from several records before it")
+        bases[:, 0] = np.where(has_base[k0:k1], np.where(inside, base_at[k0:k1] - lo + front, 0), -1)
+        yield k0, k1, rows, bases, front + hi - lo, reads
+        k0 = k1
 
 
 _PREAD_PIECE = 4 << 20  # a batch is read by several threads in pieces of this size

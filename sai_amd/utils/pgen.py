@@ -1,0 +1,297 @@
+"""PLINK 2 binary filesets (PREFIX.pgen + PREFIX.pvar + PREFIX.psam) as an input of ``score``.
+
+A ``.pgen`` holds hard calls in 2 bits and compresses them further -- sparse difference lists, one-bit rows, rows
+stored as differences from an earlier row -- so its records have variable length.  The host index
+(``sai_pgen_open``, sai_amd/csrc/pgen/pgen_index.cpp) resolves the samples, selects the rows and reads the
+``.pgen`` header: for every selected row the byte span of its record and of the record it differs from (its base,
+which may lie before the region).  The record bytes cross PCIe as they are and ``sai_pgen_decode`` expands and
+recodes them into the int8 [record][sample] block ``sai_tokenize_gt`` writes for VCF text, so everything behind the
+readers is shared with the VCF route.  REF and ALT are what the ``.pvar`` names; the format rules, the dosage table
+and what is refused are in DESIGN_INGEST.md ("PLINK 2 filesets").
+
+``load_dosage`` / ``load_dosage_device`` return what ``native_vcf.load_dosage`` /
+``device_vcf.load_dosage_device`` return.  As for a PLINK 1 fileset, one pass serves a sample that is asked for
+more than once: every request is a slot.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+
+from .. import _ffi, _ffi_pgen
+from ._ingest import check_io, default_threads, pair, pread_into, region_args, span_batches, staging
+
+BUFFER_BYTES = 32 << 20  # as the VCF route (device_vcf.BUFFER_BYTES); SAI_AMD_INGEST_BUFFER overrides it
+_MAGIC = b"\x6c\x1b"
+_EXTENSIONS = (".pgen", ".pvar", ".psam")
+_READ_THROUGH_BYTES = 64 << 10  # unselected records between two wanted ones are read along up to this many bytes
+
+
+def fileset_prefix(path) -> Optional[str]:
+    """PREFIX when ``path`` (``PREFIX.pgen`` or the bare ``PREFIX``) names a PLINK 2 fileset: the three files exist
+    and the ``.pgen`` starts with PLINK's magic bytes and a storage mode other than a ``.bed``'s.  A bare prefix that
+    is also a PLINK 1 or an EIGENSOFT fileset stays what it was."""
+    if path is None:
+        return None
+    text = os.fspath(path)
+    candidates = ([text[: -len(".pgen")]] if text.endswith(".pgen") else []) + [text]
+    for prefix in candidates:
+        if prefix and all(os.path.isfile(prefix + ext) for ext in _EXTENSIONS):
+            if prefix == text:
+                from . import eigenstrat, plink
+
+                if plink.fileset_prefix(text) is not None or eigenstrat.fileset_prefix(text) is not None:
+                    return None
+            try:
+                with open(prefix + ".pgen", "rb") as f:
+                    head = f.read(3)
+                    if head[:2] == _MAGIC and len(head) == 3 and head[2] != 0x01:
+                        return prefix
+            except OSError:
+                pass
+    return None
+
+
+def is_fileset(path) -> bool:
+    return fileset_prefix(path) is not None
+
+
+def _prefix_of(path) -> str:
+    """The prefix a reader hands to the library: the detected one, else the path as a prefix (the library
+    then says which file is missing or what is wrong with the ``.pgen``)."""
+    found = fileset_prefix(path)
+    if found is not None:
+        return found
+    text = os.fspath(path)
+    return text[: -len(".pgen")] if text.endswith(".pgen") else text
+
+
+def header_counts(path):
+    """(variant_ct, sample_ct) of the ``.pgen`` header."""
+    with open(_prefix_of(path) + ".pgen", "rb") as f:
+        head = f.read(11)
+    if len(head) < 11 or head[:2] != _MAGIC:
+        raise ValueError(f"{_prefix_of(path)}.pgen: not a PLINK 2 .pgen file")
+    return int.from_bytes(head[3:7], "little"), int.from_bytes(head[7:11], "little")
+
+
+def scan_first_last(path, chr_name: str):
+    """First and last position of the first contiguous run of ``chr_name`` in the ``.pvar`` (None, None if
+    absent): ``native_vcf.scan_first_last`` for a fileset."""
+    lib = _ffi_pgen.load_host()
+    first, last = C.c_int64(-1), C.c_int64(-1)
+    check_io(lib, lib.sai_pgen_scan(os.fsencode(_prefix_of(path)), str(chr_name).encode(), C.byref(first), C.byref(last)))
+    return (None, None) if first.value < 0 else (int(first.value), int(last.value))
+
+
+class _Index:
+    """The host index of one region: positions, the variant number and the flip flag of every selected row, the span
+    and vrtype of its record and of its base, the sample column of every slot."""
+
+    def __init__(self, lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads):
+        self.prefix = _prefix_of(path)
+        n, handle = len(samples), C.c_void_p()
+        args = region_args(self.prefix, chr_name, start, end, samples, ploidies, anc_allele_file, n_threads)
+        check_io(lib, lib.sai_pgen_open(*args, C.byref(handle)))
+        try:
+            v = [C.c_int64() for _ in range(8)]
+            check_io(lib, lib.sai_pgen_index_info(handle, *[C.byref(x) for x in v]))
+            n_rows, self.n_matched, self.n_anc, self.sample_ct, self.variant_ct, self.mode, self.first, self.last = (int(x.value) for x in v)
+            self.pos = np.empty(n_rows, dtype=np.int32)
+            self.file_row = np.empty(n_rows, dtype=np.int64)
+            self.flip = np.empty(n_rows, dtype=np.uint8)
+            self.col_of_slot = np.empty(n, dtype=np.int32)
+            self.rec = np.empty((n_rows, 3), dtype=np.int64)
+            self.base = np.empty((n_rows, 3), dtype=np.int64)
+            arrays = (self.pos, self.file_row, self.flip, self.col_of_slot, self.rec, self.base)
+            check_io(lib, lib.sai_pgen_index_copy(handle, *(a.ctypes.data_as(C.c_void_p) for a in arrays)))
+        finally:
+            lib.sai_pgen_index_close(handle)
+        self.samples = list(samples)
+        self.ploidies = np.asarray([int(p) for p in ploidies], dtype=np.int32)
+        self.n_rows, self.n_slots = n_rows, n
+        cols = self.col_of_slot
+        # the two promises that select the kernel's fast path
+        self.first_col = int(cols[0]) if n and np.array_equal(cols, np.arange(cols[0], cols[0] + n, dtype=np.int32)) else -1
+        self.uniform_ploidy = int(self.ploidies[0]) if n and bool((self.ploidies == self.ploidies[0]).all()) else 0
+
+    def batches(self, cap: int):
+        """Cut the selected rows into batches of at most ``cap`` bytes of whole records, the base of a batch's first
+        row included when it lies before the batch.  Yields ``(k0, k1, rec int64 [k1 - k0][3], base int64 [k1 - k0][3],
+        n_bytes, reads)``: the spans with their offsets counted from the start of the batch's buffer, ``reads`` =
+        [(buffer offset, file offset, bytes)]."""
+        return span_batches(self.rec, self.base, cap, _READ_THROUGH_BYTES, f"{self.prefix}.pgen")
+
+    def raise_flagged(self, status: np.ndarray, row0: int = 0) -> None:
+        """The first flagged row of ``status`` (rows ``row0 ..`` of the index) as the reader's ValueError."""
+        bad = np.flatnonzero(status)
+        if bad.size == 0:
+            return
+        k, st = row0 + int(bad[0]), int(status[bad[0]])
+        if st == _ffi_pgen.SAI_PGEN_STATUS_BAD_RECORD:
+            raise ValueError(
+                f"{self.prefix}.pgen: the record of variant {_variant_id(self.prefix, int(self.file_row[k]))} (position {int(self.pos[k])}, "
+                f"vrtype {int(self.rec[k, 2])}, {int(self.rec[k, 1])} bytes at byte {int(self.rec[k, 0])}) does not parse: the file is damaged, "
+                "or not written by the rules in DESIGN_INGEST.md"
+            )
+        if st == _ffi_pgen.SAI_PGEN_STATUS_BAD_INDEX:
+            raise ValueError(f"{self.prefix}.pgen: variant {int(self.file_row[k]) + 1} was decoded with an index outside its range")
+        slot = self.n_slots - st
+        raise ValueError(
+            f"{self.prefix}.pgen: heterozygous call of sample {self.samples[slot]} at variant {_variant_id(self.prefix, int(self.file_row[k]))} "
+            f"(position {int(self.pos[k])}), but the sample is configured with ploidy 1: a fileset has no phase to pick an allele by"
+        )
+
+
+def _variant_id(prefix: str, file_row: int) -> str:
+    """The ID of record line ``file_row`` of the ``.pvar`` (error path only): column 3 under a header line, column 2
+    of a ``.bim``."""
+    try:
+        with open(prefix + ".pvar", "rb") as f:
+            k, column = -1, 1
+            for line in f:
+                fields = line.split()
+                if not fields or fields[0].startswith(b"##"):
+                    continue
+                if fields[0].startswith(b"#"):
+                    column = 2
+                    continue
+                k += 1
+                if k == file_row:
+                    return fields[column].decode("utf-8", "replace")
+    except (OSError, IndexError):
+        pass
+    return f"#{file_row + 1}"
+
+
+def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[int], start: Optional[int] = None,
+                end: Optional[int] = None, anc_allele_file: Optional[str] = None, n_threads: Optional[int] = None,
+                buffer_bytes: Optional[int] = None):  # fmt: skip
+    """(pos int32 [n], dosage int8 [n][len(samples)], n_matched, n_anc_entries) for one region, decoded on
+    the host (``sai_pgen_decode_host``): the ``SAI_AMD_INGEST=host`` route and the yardstick of the kernel."""
+    lib = _ffi_pgen.load_host()
+    n_threads = n_threads or default_threads()
+    idx = _Index(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads)
+    n = idx.n_slots
+    dos = np.empty((idx.n_rows, n), dtype=np.int8)
+    if n == 0 or idx.n_rows == 0:
+        return idx.pos, dos, idx.n_matched, idx.n_anc
+    cap = int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
+    status = np.empty(idx.n_rows, dtype=np.int32)
+    flip = idx.flip
+    buf = None
+    fd = os.open(idx.prefix + ".pgen", os.O_RDONLY)
+    try:
+        for k0, k1, rec, base, nbytes, reads in idx.batches(cap):
+            if buf is None or buf.size < nbytes:
+                buf = np.empty(nbytes, dtype=np.uint8)
+            pread_into(fd, memoryview(buf), reads, idx.prefix + ".pgen")
+            check_io(lib, lib.sai_pgen_decode_host(
+                buf.ctypes.data_as(C.c_void_p), nbytes, k1 - k0, rec.ctypes.data_as(C.c_void_p), base.ctypes.data_as(C.c_void_p),
+                flip[k0:k1].ctypes.data_as(C.c_void_p), idx.sample_ct, n, idx.col_of_slot.ctypes.data_as(C.c_void_p),
+                idx.ploidies.ctypes.data_as(C.c_void_p), dos[k0:k1].ctypes.data_as(C.c_void_p),
+                status[k0:k1].ctypes.data_as(C.c_void_p), n_threads,
+            ))  # fmt: skip
+    finally:
+        os.close(fd)
+    idx.raise_flagged(status)
+    return idx.pos, dos, idx.n_matched, idx.n_anc
+
+
+def release_buffers(eng) -> None:
+    """Drop the staging ``load_dosage_device`` keeps between calls."""
+    st = eng.__dict__.pop("_pgen_state", None)
+    if st:
+        st["stream"].synchronize()
+        st.clear()
+
+
+def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidies: Sequence[int],
+                       start: Optional[int] = None, end: Optional[int] = None, anc_allele_file: Optional[str] = None,
+                       n_threads: Optional[int] = None, buffer_bytes: Optional[int] = None, trace: Optional[dict] = None):  # fmt: skip
+    """(pos int32 host array [n], dosage int8 DEVICE tensor [n][len(samples)], n_matched, n_anc_entries):
+    ``load_dosage`` with the result left in HBM.  The records of a batch are ``pread`` into two pinned buffers in
+    turn, copied on a side stream and decoded behind the copy, so the file read of batch k + 1 runs under the copy
+    and the kernel of batch k.  ``trace`` (a dict) collects host-clock seconds per phase: always ``index`` and
+    ``file_read``; with ``trace["serial"]`` set the side stream is synchronised behind every copy and every kernel,
+    so ``h2d`` and ``decode`` are timed on their own (and nothing overlaps)."""
+    import time
+
+    import torch
+
+    _ffi_pgen.load()
+    lib = eng.lib
+    t0 = time.perf_counter()
+    idx = _Index(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads)
+    if trace is not None:
+        trace["index"] = trace.get("index", 0.0) + time.perf_counter() - t0
+        trace["pgen_bytes"] = 0
+    n = idx.n_slots
+    dos = torch.empty((idx.n_rows, n), dtype=torch.int8, device=eng.device)
+    if n == 0 or idx.n_rows == 0:
+        return idx.pos, dos, idx.n_matched, idx.n_anc
+    cap = int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
+    plan = idx.batches(cap)
+    first = next(plan)  # a buffer smaller than one record is refused before anything is page-locked
+    # two pinned staging buffers, their device twins and the side stream, kept for the next call
+    st = staging(eng, "_pgen_state", cap, lambda: {"pinned": pair(cap), "rows": pair(cap, device=eng.device),
+                                                   "stream": torch.cuda.Stream(device=eng.device)})  # fmt: skip
+    pinned, dev_rows, side = st["pinned"], st["rows"], st["stream"]
+    status = torch.empty((idx.n_rows,), dtype=torch.int32, device=eng.device)
+    cols_dev = None if idx.first_col >= 0 else torch.from_numpy(idx.col_of_slot).to(eng.device)
+    ploidy_dev = None if idx.uniform_ploidy else torch.from_numpy(idx.ploidies).to(eng.device)
+    copied = [None, None]  # per buffer: the event behind its last H2D copy
+    keep = []
+    fd = os.open(idx.prefix + ".pgen", os.O_RDONLY)
+    try:
+        side.wait_stream(torch.cuda.current_stream(eng.device))  # `dos` and `status` were allocated on the current stream
+        b = 0
+
+        def batches():
+            yield first
+            yield from plan
+
+        for k0, k1, rec, base, nbytes, reads in batches():
+            if copied[b] is not None:
+                copied[b].synchronize()  # the copy two batches back has left this pinned buffer
+            t1 = time.perf_counter()
+            pread_into(fd, memoryview(pinned[b].numpy()), reads, idx.prefix + ".pgen")
+            if trace is not None:
+                trace["file_read"] = trace.get("file_read", 0.0) + time.perf_counter() - t1
+                trace["pgen_bytes"] += nbytes
+            serial = trace is not None and trace.get("serial")
+            with torch.cuda.stream(side):
+                t1 = time.perf_counter()
+                dev_rows[b][:nbytes].copy_(pinned[b][:nbytes], non_blocking=True)
+                copied[b] = torch.cuda.Event()
+                copied[b].record(side)
+                if serial:
+                    side.synchronize()
+                    trace["h2d"] = trace.get("h2d", 0.0) + time.perf_counter() - t1
+                    t1 = time.perf_counter()
+                d_rec = torch.from_numpy(rec).to(eng.device, non_blocking=True)
+                d_base = torch.from_numpy(base).to(eng.device, non_blocking=True)
+                d_flip = torch.from_numpy(idx.flip[k0:k1]).to(eng.device, non_blocking=True)
+                keep.append((d_rec, d_base, d_flip))
+                _ffi.check(
+                    lib.sai_pgen_decode(eng.ctx, C.c_void_p(dev_rows[b].data_ptr()), nbytes, k1 - k0, eng._ptr(d_rec), eng._ptr(d_base),
+                                        eng._ptr(d_flip), idx.sample_ct, n, eng._ptr(cols_dev), idx.first_col, eng._ptr(ploidy_dev),
+                                        idx.uniform_ploidy, C.c_void_p(dos.data_ptr()), k0, C.c_void_p(status.data_ptr() + 4 * k0),
+                                        C.c_void_p(side.cuda_stream))
+                )  # fmt: skip
+                if serial:
+                    side.synchronize()
+                    trace["decode"] = trace.get("decode", 0.0) + time.perf_counter() - t1
+            b ^= 1
+    finally:
+        os.close(fd)
+        side.synchronize()  # also on an error: the staging buffers are reused by the next call
+    flagged = status.cpu().numpy() if bool(status.any()) else None
+    if flagged is not None:
+        idx.raise_flagged(flagged)
+    torch.cuda.current_stream(eng.device).wait_stream(side)
+    return idx.pos, dos, idx.n_matched, idx.n_anc
