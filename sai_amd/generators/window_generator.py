@@ -61,12 +61,14 @@ class WindowGenerator(DataGenerator):
         num_src: int = 1,
         resident: bool = False,
         preloaded=None,
+        layout: str = "int8",
     ):
         """``resident=True`` (the batched GPU driver, ChunkPreprocessor): the region is streamed to
         the GPU and tokenised there, the populations exist only as tiled blocks in HBM and ``get()``
         is not available; otherwise the populations are host matrices, as in the reference.
         ``preloaded`` = what ``read_data_device`` returned for exactly this region (the caller read it
-        before it knew the chunk bounds, ChunkPreprocessor.preload)."""
+        before it knew the chunk bounds, ChunkPreprocessor.preload).  ``layout="packed2"`` (with ``resident``): the
+        populations are read as ``PackedPop`` blocks (``read_data_device``)."""
         if win_len <= 0:
             raise ValueError("`win_len` must be greater than 0.")
         if win_step < 0:
@@ -83,7 +85,7 @@ class WindowGenerator(DataGenerator):
             from ..engine import Engine
             from ..utils.read_data import read_data_device
 
-            results, pos_dev = read_data_device(Engine.get(), **kw)
+            results, pos_dev = read_data_device(Engine.get(), **kw, layout=layout)
         else:
             results = read_dosage_data(**kw)  # = read_data(..., is_phased=False, no filters): window_generator.py:105-120
         self._setup(
@@ -128,8 +130,8 @@ class WindowGenerator(DataGenerator):
     def from_resident(cls, chr_name, pos: np.ndarray, pos_dev, ref: dict, tgt: dict, src: dict, win_len: int,
                       win_step: int, ploidy_config, start: int = None, end: int = None, out: Optional[dict] = None):  # fmt: skip
         """Build from blocks that already live in HBM: ``ref`` / ``tgt`` / ``src`` / ``out`` map
-        population -> TiledPop over the sites of ``pos`` (host int32 array; ``pos_dev`` its device
-        copy).  ``get()`` (per-window host matrices for the plugin classes) is not available on such
+        population -> TiledPop (or PackedPop: the 2-bit layout) over the sites of ``pos`` (host int32 array;
+        ``pos_dev`` its device copy).  ``get()`` (per-window host matrices for the plugin classes) is not available on such
         a generator; the batched path (FeaturePreprocessor.run_windows) is."""
         data = lambda d: {k: ChromosomeData(POS=pos, REF=None, ALT=None, GT=v) for k, v in d.items()}  # noqa: E731
         names = lambda d: {k: [f"{k}_{i}" for i in range(v.n_ind)] for k, v in d.items()}  # noqa: E731
@@ -250,8 +252,8 @@ class WindowGenerator(DataGenerator):
     def device_blocks(self, eng) -> dict:
         """{(group, population): TiledPop} of every loaded population: host matrices are uploaded
         and re-tiled once per generator; blocks that already live in HBM (``from_resident``) are
-        handed through."""
-        from ..engine import TiledPop
+        handed through -- a PackedPop as it is, where its reader put it: the placement search moves tiled blocks."""
+        from ..engine import PackedPop, TiledPop
 
         cache = self.__dict__.setdefault("_device_blocks", {})
         fresh = False
@@ -261,12 +263,12 @@ class WindowGenerator(DataGenerator):
         for group, data in groups:
             for pop, cd in data.items():
                 if (group, pop) not in cache:
-                    cache[(group, pop)] = cd.GT if isinstance(cd.GT, TiledPop) else eng.tile(cd.GT)
-                    fresh = True
+                    cache[(group, pop)] = cd.GT if isinstance(cd.GT, (TiledPop, PackedPop)) else eng.tile(cd.GT)
+                    fresh = fresh or not isinstance(cd.GT, PackedPop)
         if fresh:  # big populations are settled next to the largest one once (placement.py): same bytes, maybe elsewhere
             from ..placement import settle_block
 
-            keys = list(cache)
+            keys = [k for k in cache if not isinstance(cache[k], PackedPop)]
             owner = {(group, pop): cd for group, data in groups for pop, cd in data.items()}
             arena: list = []
             settled = settle_block(eng, [cache[k] for k in keys], arena=arena)

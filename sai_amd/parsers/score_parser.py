@@ -52,6 +52,7 @@ def _run_score(args: argparse.Namespace) -> None:
         output_file=args.output,
         config=args.config,
         num_workers=args.num_workers,
+        layout=args.layout,
     )
 
 
@@ -89,4 +90,9 @@ def add_score_parser(subparsers) -> None:
     # one worker process each (sai.py:42); the default, 1, is the reference's behaviour
     parser.add_argument("--num-workers", dest="num_workers", type=positive_int, default=None,
                         help="Number of GPUs to use, one worker process per GPU. Default: $SAI_AMD_GPUS, else 1.")  # fmt: skip
+    # not a flag of the reference: how the genotypes lie in GPU memory
+    parser.add_argument("--layout", choices=("int8", "packed2"), default=None,
+                        help="Genotype layout in GPU memory: int8 (one byte per call, every input and statistic) or packed2 "
+                        "(two bits per call, decoded straight from a PLINK 1 fileset given with --bfile; U and Q only, one "
+                        "worker). Default: $SAI_AMD_LAYOUT, else int8.")  # fmt: skip
     parser.set_defaults(runner=_run_score, score_parser=parser)

@@ -27,7 +27,9 @@ class ChunkPreprocessor(DataPreprocessor):
         stat_config,
         anc_allele_file: str = None,
         num_src: int = 1,
+        layout: str = "int8",
     ):
+        self.layout = layout  # "packed2": a PLINK 1 fileset decoded straight into the 2-bit layout, U and Q only
         self.vcf_file = vcf_file
         self.ref_ind_file = ref_ind_file
         self.tgt_ind_file = tgt_ind_file
@@ -43,6 +45,7 @@ class ChunkPreprocessor(DataPreprocessor):
             output_file=output_file,
             stat_config=stat_config,
             anc_allele_available=anc_allele_file is not None,
+            layout=layout,
         )
 
     def run(self, chr_name: str, start: int, end: int) -> list[dict[str, Any]]:
@@ -96,6 +99,7 @@ class ChunkPreprocessor(DataPreprocessor):
             anc_allele_file=self.anc_allele_file,
             num_src=self.num_src,
             resident=os.environ.get("SAI_AMD_INGEST", "device") != "host",
+            layout=self.layout,
         )
 
     # transport hooks of sai_amd.distributed.run_sharded / sai_amd.multiprocessing.mp_pool

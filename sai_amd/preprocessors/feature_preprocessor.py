@@ -130,10 +130,13 @@ def _file_order_semantics(res, uq_names, lo, hi, pos_sorted, file_order) -> None
 
 
 class FeaturePreprocessor(DataPreprocessor):
-    def __init__(self, output_file: str, stat_config, anc_allele_available: bool = False):
+    def __init__(self, output_file: str, stat_config, anc_allele_available: bool = False, layout: str = "int8"):
+        if layout not in ("int8", "packed2"):
+            raise ValueError("layout must be 'int8' or 'packed2'")
         self.output_file = output_file
         self.anc_allele_available = anc_allele_available
         self.stat_config = stat_config
+        self.layout = layout  # "packed2": the populations of the generator are PackedPop blocks (_score_packed)
 
     # -- helpers ---------------------------------------------------------------------------
 
@@ -295,6 +298,8 @@ class FeaturePreprocessor(DataPreprocessor):
                 if sink is not None:
                     sink(batch.combos[-1])
             return batch
+        if self.layout == "packed2":
+            return self._score_packed(wg, combos, names, batch, sink)
 
         import torch
 
@@ -467,6 +472,70 @@ class FeaturePreprocessor(DataPreprocessor):
                     ],
                     axis=1,
                 )  # fmt: skip
+            if sink is not None:
+                sink(cb)
+        return batch
+
+    def _score_packed(self, wg, combos, names, batch, sink) -> WindowBatch:
+        """``score_windows`` over populations that were decoded straight into the 2-bit layout (``PackedPop``, the
+        generator was built with ``layout="packed2"``): U and Q only, every combination by one
+        ``ResidentScorer(layout="packed2")`` that streams the blocks as they are (``packed_scorer``) -- the fused
+        packed2 site pass and the windows stage, the records of the int8 path bit for bit.  The int8 branches (shared counts, parts, DD, the ABBA-BABA family) have no packed
+        form and are not touched."""
+        from .. import _ffi
+        from ..engine import Engine
+        from ..packed_scorer import packed_scorer
+        from ..resident import ResidentBlock
+        from ..stats.stat_utils import _check_ploidy, validate_thresholds
+
+        other = [n for n in names if n not in _HIP_STATS]
+        if other:
+            raise ValueError(f"the packed2 layout serves U and Q only, but {other[0]} is configured")
+        eng = Engine.get()
+        pc = wg.ploidy_config
+        blocks = wg.device_blocks(eng)
+        for ref_pop, tgt_pop, src_comb, out_pop in combos:
+            al = wg.aligned(ref_pop, tgt_pop, src_comb, out_pop)
+            if al.rows is not None or al.uniq is not None or al.file_order is not None or al.segments is not None:
+                raise ValueError("the packed2 layout needs positions that ascend without a repeat; read this input with the int8 layout")
+            pos = al.pos_rows
+            win = np.asarray(wg.tgt_windows[tgt_pop], dtype=np.int64).reshape(-1, 2)
+            src_ploidies = pc.get_ploidy("src")
+            ploidy = [pc.get_ploidy("ref", ref_pop), pc.get_ploidy("tgt", tgt_pop)] + list(src_ploidies)
+            n_eff = min(len(src_comb), len(src_ploidies))
+            if n_eff > _ffi.SAI_FUSED_SRC:
+                raise ValueError(f"the packed2 layout streams at most {_ffi.SAI_FUSED_SRC} source populations in one pass")
+            # U and Q that share w, the source conditions and the polarity mode are ONE parameter set, as on the int8 path
+            sets, set_of, merged = [], [], {}
+            for name in names:
+                kw = self._stat_kwargs(name, ref_pop, tgt_pop)
+                validate_thresholds(kw["w"], kw["y_list"], len(src_comb))
+                key = (float(kw["w"]), tuple((op, float(y)) for op, y in kw["y_list"]), bool(kw["anc_allele_available"]))
+                field, value = ("x", kw["x"]) if name == "U" else ("quantile", kw["quantile"])
+                at = next((i for i in merged.get(key, ()) if field not in sets[i][1]), None)
+                if at is None:
+                    at = len(sets)
+                    sets.append((kw, {}))
+                    merged.setdefault(key, []).append(at)
+                sets[at][1][field] = value
+                set_of.append(at)
+            sets = [_ffi.make_params(kw["w"], got.get("x", 0.0), got.get("quantile", 0.5), kw["y_list"],
+                                     kw["anc_allele_available"], n_src=n_eff) for kw, got in sets]  # fmt: skip
+            for p in ploidy[: 2 + len(src_comb)]:
+                _check_ploidy(p)
+            cb = ComboBatch(ref_pop, tgt_pop, tuple(src_comb), out_pop, win, np.zeros(len(win), np.int32), list(names),
+                            pos_dtype=np.dtype(pos.dtype).name)  # fmt: skip
+            batch.combos.append(cb)
+            if names and len(win) and pos.size:
+                keys = [("ref", ref_pop), ("tgt", tgt_pop)] + [("src", s) for s in src_comb[:n_eff]]
+                block = ResidentBlock([blocks[k] for k in keys], ploidy[: 2 + n_eff], wg.device_positions(eng, pos))
+                scorer = packed_scorer(eng, block, win, sets, cap_u=1 << 16, cap_q=1 << 16, fetch_lists=1 << 16)
+                try:
+                    scorer.step()
+                    cb.uq = _rows_per_statistic(scorer.results(grow=True), set_of)
+                finally:
+                    scorer.close()
+                cb.nsnps = cb.uq.records[0]["n_sites"].astype(np.int32)
             if sink is not None:
                 sink(cb)
         return batch

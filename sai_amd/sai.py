@@ -69,12 +69,43 @@ def require_polarised_input(stat_config, anc_allele_file) -> None:
         )
 
 
-def chunk_preprocessor_for(cfg: GlobalConfig, vcf_file, win_len, win_step, output_file, anc_allele_file) -> ChunkPreprocessor:
+def chunk_preprocessor_for(cfg: GlobalConfig, vcf_file, win_len, win_step, output_file, anc_allele_file,
+                           layout: str = "int8") -> ChunkPreprocessor:
     """The chunk driver of a run: the sample lists come from the configuration's ``populations``
     section (sai.py:95-107).  Shared by ``score`` and ``sai_amd.distributed.score_sharded``."""
     files = {group: cfg.populations.get_population(group) for group in ("ref", "tgt", "src", "outgroup")}
     return ChunkPreprocessor(vcf_file, files["ref"], files["tgt"], files["src"], files["outgroup"], win_len, win_step,
-                             output_file, cfg.ploidies, cfg.statistics, anc_allele_file=anc_allele_file)  # fmt: skip
+                             output_file, cfg.ploidies, cfg.statistics, anc_allele_file=anc_allele_file, layout=layout)  # fmt: skip
+
+
+LAYOUTS = ("int8", "packed2")
+
+
+def resolve_layout(layout=None) -> str:
+    """The genotype layout of a run: the argument, else ``SAI_AMD_LAYOUT``, else ``int8``."""
+    layout = layout or os.environ.get("SAI_AMD_LAYOUT") or "int8"
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be one of {', '.join(LAYOUTS)}, not {layout!r}.")
+    return layout
+
+
+def require_packed2_input(vcf_file, config: str, num_workers: int) -> None:
+    """What ``layout="packed2"`` cannot serve is refused here, before any genotype is read: the layout is decoded
+    from PLINK 1 ``.bed`` rows on the GPU of one process and feeds the U / Q site pass."""
+    from . import launcher
+    from .utils import plink
+    from .utils.filesets import reader_for
+
+    if num_workers > 1 or launcher.in_rank_job():
+        raise ValueError("layout 'packed2' runs in one process on one GPU: use num_workers=1 outside a rank job, or layout 'int8'.")
+    if os.environ.get("SAI_AMD_INGEST", "device") == "host":
+        raise ValueError("layout 'packed2' is decoded on the GPU: it cannot be combined with SAI_AMD_INGEST=host.")
+    if reader_for(vcf_file) is not plink:
+        raise ValueError(f"layout 'packed2' reads a PLINK 1 fileset (.bed + .bim + .fam) only, which {vcf_file} is not.")
+    stats = load_config(config).statistics.root
+    other = [name for name, value in stats.items() if name not in ("U", "Q") and value is not False]
+    if other:
+        raise ValueError(f"layout 'packed2' serves the U and Q statistics only, but {other[0]} is configured.")
 
 
 def _reads_in_one_pass(vcf_file: str) -> bool:
@@ -141,7 +172,7 @@ def _scan_while_reading(driver: ChunkPreprocessor, vcf_file: str, chr_name: str)
     return span, preloaded
 
 
-def chunks_for_memory(vcf_file: str) -> int:
+def chunks_for_memory(vcf_file: str, layout: str = "int8") -> int:
     """How many ChunkGenerator chunks a one-process `score` cuts the chromosome into so that a chunk's genotypes
     fit the GPU: 1 (the reference's one-process form, sai.py:86-93 with one worker) unless the file promises more
     int8 genotype bytes than the budget -- then ceil(bytes / budget), the grain the sharded route already uses
@@ -150,11 +181,15 @@ def chunks_for_memory(vcf_file: str) -> int:
     text about twelvefold), of which one int8 dosage stays resident -- besides the reader's staging and the tiled
     copy per population, hence a budget of a quarter of the free HBM.  ``SAI_AMD_HBM_BUDGET_BYTES`` overrides it.
     A PLINK ``.bed`` and a packed ``.geno`` hold four genotypes per byte: 4 x their size stays resident; a text
-    ``.geno`` holds one: 1 x."""
+    ``.geno`` holds one: 1 x.  With ``layout="packed2"`` a ``.bed`` is never widened: 1 x its size stays resident."""
     from .utils.filesets import resident_bytes
 
     try:
         resident = resident_bytes(vcf_file)
+        if layout == "packed2" and resident is not None:
+            from .utils import plink
+
+            resident = os.path.getsize(plink.fileset_prefix(vcf_file) + ".bed")
         if resident is None:
             size = os.path.getsize(vcf_file)
             resident = size * 3 if str(vcf_file).endswith((".gz", ".bgz")) else size // 4
@@ -200,7 +235,7 @@ def _score_cli_arguments(vcf_file, chr_name, win_len, win_step, anc_allele_file,
 
 
 def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_file: str, output_file: str, config: str,
-          num_workers: int) -> None:  # fmt: skip
+          num_workers: int, layout: str = None) -> None:  # fmt: skip
     """Sliding-window scores of one chromosome, written as the reference writes them (TSV +
     ``.U.log`` + ``.Q.log``; interface of sai.py:33-42).
 
@@ -210,12 +245,20 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
     list into ``N * 8`` ChunkGenerator chunks, each rank reading and scoring its own contiguous share on
     its own GPU, with one final gather to rank 0, which writes the files -- byte-identical to the
     one-process files for any N (``sai_amd.distributed.score_sharded``).  Inside such a job
-    (``WORLD_SIZE`` > 1: torchrun's environment) the call IS a rank and takes the sharded route."""
+    (``WORLD_SIZE`` > 1: torchrun's environment) the call IS a rank and takes the sharded route.
+
+    ``layout`` = ``"int8"`` (the default; ``SAI_AMD_LAYOUT`` overrides it) or ``"packed2"``: a PLINK 1 fileset is
+    decoded straight into the 2-bit layout and U / Q are scored on it -- four times as many sites per chunk, the same
+    files byte for byte.  What that route cannot serve is a ValueError before anything is read
+    (``require_packed2_input``); a missing call in a row flipped by the ancestral allele (dosage 4) is one while reading."""
     from . import launcher
 
     num_workers = 1 if num_workers is None else int(num_workers)
     if num_workers < 1:
         raise ValueError("`num_workers` must be a positive integer.")
+    layout = resolve_layout(layout)
+    if layout == "packed2":
+        require_packed2_input(vcf_file, config, num_workers)
     if launcher.in_rank_job():
         _score_over_ranks(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config)
         return
@@ -232,9 +275,9 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
         return
     cfg = load_config(config)
     require_polarised_input(cfg.statistics, anc_allele_file)
-    driver = chunk_preprocessor_for(cfg, vcf_file, win_len, win_step, output_file, anc_allele_file)
+    driver = chunk_preprocessor_for(cfg, vcf_file, win_len, win_step, output_file, anc_allele_file, layout=layout)
     span, preloaded = None, None
-    n_chunks = chunks_for_memory(vcf_file)  # 1 unless the chromosome's genotypes would not fit the GPU at once
+    n_chunks = chunks_for_memory(vcf_file, layout)  # 1 unless the chromosome's genotypes would not fit the GPU at once
     if n_chunks == 1 and _reads_in_one_pass(vcf_file):
         span, preloaded = _scan_while_reading(driver, vcf_file, str(chr_name))
     chunks = ChunkGenerator(vcf_file=vcf_file, chr_name=chr_name, window_size=win_len, step_size=win_step,

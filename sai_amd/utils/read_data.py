@@ -192,7 +192,7 @@ def _assemble(samples_by_group, ploidy_config, block) -> dict:
 
 
 def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file,
-                     out_ind_file=None, anc_allele_file=None, start: int = None, end: int = None):
+                     out_ind_file=None, anc_allele_file=None, start: int = None, end: int = None, layout: str = "int8"):
     """``read_data`` with the genotypes left in HBM: one streaming pass over the file (text over PCIe,
     tokenised on the GPU, ``device_vcf.load_dosage_device``) for all populations and ploidies, then one
     re-tiling launch per population straight from the shared [record][sample] block.  Returns
@@ -200,12 +200,20 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
     ``TiledPop``; ``pos_dev`` = the int32 device copy of the positions (None without data).  A PLINK 1
     fileset takes the same way with its own reader (``plink.load_dosage_device``: ``.bed`` rows over PCIe,
     decoded on the GPU), and so does an EIGENSOFT one (``eigenstrat.load_dosage_device``); there a slot is a
-    (sample, ploidy) request, so one pass always serves all."""
+    (sample, ploidy) request, so one pass always serves all.
+
+    ``layout="packed2"`` (a PLINK 1 fileset only): every ``GT`` is a ``PackedPop``, decoded from the ``.bed`` rows
+    straight into the 2-bit layout (``plink.load_packed_device``); no int8 block is built on the way."""
     import torch
 
     from .filesets import reader_for
 
     reader = reader_for(vcf_file)
+    if layout == "packed2":
+        return _read_packed_device(eng, reader, vcf_file, str(chr_name), ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file,
+                                   out_ind_file, anc_allele_file, start, end)  # fmt: skip
+    if layout != "int8":
+        raise ValueError("layout must be 'int8' or 'packed2'")
     fileset = reader is not None
     if fileset:
         load_dosage_device = reader.load_dosage_device
@@ -255,6 +263,38 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
         else:  # the population's samples were tokenised in different passes: gather its columns first
             tiled = eng._tile_device(torch.stack([blocks[k][:, c] for k, c in where_cols], dim=1).contiguous())
         return ChromosomeData(POS=pos, REF=None, ALT=None, GT=tiled)
+
+    pos_dev = torch.from_numpy(pos).to(eng.device) if n_matched else None
+    return _assemble(samples_by_group, ploidy_config, block), pos_dev
+
+
+def _read_packed_device(eng, reader, vcf_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
+                        anc_allele_file, start, end):
+    """``read_data_device(..., layout="packed2")``: one pass over the ``.bed``, one packed2 block per population."""
+    import torch
+
+    from . import plink
+
+    if reader is not plink:
+        raise ValueError(f"{vcf_file}: the packed2 layout is read from a PLINK 1 fileset (.bed + .bim + .fam) only")
+    samples_by_group = _parse_groups(ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file)
+    wanted = list(_wanted(samples_by_group, ploidy_config))
+    if not any(names for _, names, _ in wanted):
+        return {"outgroup": (None, None), **{group: (None, samples) for group, samples in samples_by_group.items()}}, None
+    where = chr_name if start is None and end is None else f"{chr_name}:{start}-{end}"
+    try:
+        pos, packed, n_matched, n_anc = plink.load_packed_device(eng, vcf_file, chr_name, [(names, ploidy) for _, names, ploidy in wanted],
+                                                                 start, end, anc_allele_file)  # fmt: skip
+    except FileNotFoundError:
+        raise
+    except Exception as e:  # utils.py:139-140
+        raise ValueError(f"Failed to read VCF file {vcf_file} from {where}: {e}") from e
+    _check_anc_found(anc_allele_file, n_matched, n_anc, chr_name, start, end)
+    in_order = iter(packed)  # _assemble asks for the populations in the order _wanted names them
+
+    def block(population, pop_names, ploidy):
+        pop = next(in_order)
+        return ChromosomeData(POS=pos, REF=None, ALT=None, GT=pop) if n_matched else None
 
     pos_dev = torch.from_numpy(pos).to(eng.device) if n_matched else None
     return _assemble(samples_by_group, ploidy_config, block), pos_dev
