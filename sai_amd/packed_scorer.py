@@ -1,8 +1,8 @@
 """``ResidentScorer(layout="packed2")`` over populations that are packed already.
 
 ``ResidentScorer`` re-encodes the tiled int8 populations of its block with ``Engine.pack2`` when it is built.  A
-PLINK 1 fileset read with ``layout="packed2"`` arrives as ``PackedPop`` blocks (``plink.load_packed_device``: the
-``.bed`` rows decoded straight into the layout), and those are streamed as they are: the scorer is handed the engine
+PLINK 1 or PLINK 2 fileset read with ``layout="packed2"`` arrives as ``PackedPop`` blocks (``plink.load_packed_device``
+/ ``pgen.load_packed_device``: the ``.bed`` rows or ``.pgen`` records decoded straight into the layout), and those are streamed as they are: the scorer is handed the engine
 through ``_KeepPacked``, whose ``pack2`` passes a ``PackedPop`` through and re-encodes anything else.  Everything
 else of the scorer -- the fused packed2 site pass, the windows stage, the records -- is ``ResidentScorer``'s own.
 

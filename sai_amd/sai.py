@@ -91,16 +91,17 @@ def resolve_layout(layout=None) -> str:
 
 def require_packed2_input(vcf_file, config: str, num_workers: int) -> None:
     """What ``layout="packed2"`` cannot serve is refused here, before any genotype is read: the layout is decoded
-    from PLINK 1 ``.bed`` rows on the GPU of one process and feeds the U / Q site pass."""
+    from PLINK 1 ``.bed`` rows or PLINK 2 ``.pgen`` records on the GPU of one process and feeds the U / Q site pass.
+    (The sentence about the input predates the ``.pgen``: it is pinned word for word, and still names PLINK 1 only.)"""
     from . import launcher
-    from .utils import plink
+    from .utils import pgen, plink
     from .utils.filesets import reader_for
 
     if num_workers > 1 or launcher.in_rank_job():
         raise ValueError("layout 'packed2' runs in one process on one GPU: use num_workers=1 outside a rank job, or layout 'int8'.")
     if os.environ.get("SAI_AMD_INGEST", "device") == "host":
         raise ValueError("layout 'packed2' is decoded on the GPU: it cannot be combined with SAI_AMD_INGEST=host.")
-    if reader_for(vcf_file) is not plink:
+    if reader_for(vcf_file) not in (plink, pgen):
         raise ValueError(f"layout 'packed2' reads a PLINK 1 fileset (.bed + .bim + .fam) only, which {vcf_file} is not.")
     stats = load_config(config).statistics.root
     other = [name for name, value in stats.items() if name not in ("U", "Q") and value is not False]
@@ -181,15 +182,21 @@ def chunks_for_memory(vcf_file: str, layout: str = "int8") -> int:
     text about twelvefold), of which one int8 dosage stays resident -- besides the reader's staging and the tiled
     copy per population, hence a budget of a quarter of the free HBM.  ``SAI_AMD_HBM_BUDGET_BYTES`` overrides it.
     A PLINK ``.bed`` and a packed ``.geno`` hold four genotypes per byte: 4 x their size stays resident; a text
-    ``.geno`` holds one: 1 x.  With ``layout="packed2"`` a ``.bed`` is never widened: 1 x its size stays resident."""
+    ``.geno`` holds one: 1 x.  With ``layout="packed2"`` a ``.bed`` is never widened: 1 x its size stays resident; a
+    ``.pgen`` is compressed, so its header's counts say it: variant_ct x ceil(sample_ct / 4)."""
     from .utils.filesets import resident_bytes
 
     try:
         resident = resident_bytes(vcf_file)
         if layout == "packed2" and resident is not None:
-            from .utils import plink
+            from .utils import pgen, plink
+            from .utils.filesets import reader_for
 
-            resident = os.path.getsize(plink.fileset_prefix(vcf_file) + ".bed")
+            if reader_for(vcf_file) is pgen:
+                variant_ct, sample_ct = pgen.header_counts(vcf_file)
+                resident = variant_ct * -(-sample_ct // 4)
+            else:
+                resident = os.path.getsize(plink.fileset_prefix(vcf_file) + ".bed")
         if resident is None:
             size = os.path.getsize(vcf_file)
             resident = size * 3 if str(vcf_file).endswith((".gz", ".bgz")) else size // 4
@@ -247,8 +254,8 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
     one-process files for any N (``sai_amd.distributed.score_sharded``).  Inside such a job
     (``WORLD_SIZE`` > 1: torchrun's environment) the call IS a rank and takes the sharded route.
 
-    ``layout`` = ``"int8"`` (the default; ``SAI_AMD_LAYOUT`` overrides it) or ``"packed2"``: a PLINK 1 fileset is
-    decoded straight into the 2-bit layout and U / Q are scored on it -- four times as many sites per chunk, the same
+    ``layout`` = ``"int8"`` (the default; ``SAI_AMD_LAYOUT`` overrides it) or ``"packed2"``: a PLINK 1 or PLINK 2 fileset
+    is decoded straight into the 2-bit layout and U / Q are scored on it -- four times as many sites per chunk, the same
     files byte for byte.  What that route cannot serve is a ValueError before anything is read
     (``require_packed2_input``); a missing call in a row flipped by the ancestral allele (dosage 4) is one while reading."""
     from . import launcher

@@ -202,8 +202,9 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
     decoded on the GPU), and so does an EIGENSOFT one (``eigenstrat.load_dosage_device``); there a slot is a
     (sample, ploidy) request, so one pass always serves all.
 
-    ``layout="packed2"`` (a PLINK 1 fileset only): every ``GT`` is a ``PackedPop``, decoded from the ``.bed`` rows
-    straight into the 2-bit layout (``plink.load_packed_device``); no int8 block is built on the way."""
+    ``layout="packed2"`` (a PLINK 1 or a PLINK 2 fileset): every ``GT`` is a ``PackedPop``, decoded from the ``.bed``
+    rows or the ``.pgen`` records straight into the 2-bit layout (the reader's ``load_packed_device``); no int8 block
+    is built on the way."""
     import torch
 
     from .filesets import reader_for
@@ -270,21 +271,23 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
 
 def _read_packed_device(eng, reader, vcf_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
                         anc_allele_file, start, end):
-    """``read_data_device(..., layout="packed2")``: one pass over the ``.bed``, one packed2 block per population."""
+    """``read_data_device(..., layout="packed2")``: one pass over the ``.bed`` or the ``.pgen`` with the reader's
+    ``load_packed_device``, one packed2 block per population."""
     import torch
 
-    from . import plink
+    from . import pgen, plink
 
-    if reader is not plink:
-        raise ValueError(f"{vcf_file}: the packed2 layout is read from a PLINK 1 fileset (.bed + .bim + .fam) only")
+    if reader is not plink and reader is not pgen:
+        raise ValueError(f"{vcf_file}: the packed2 layout is read from a PLINK 1 fileset (.bed + .bim + .fam) or a PLINK 2 fileset "
+                         "(.pgen + .pvar + .psam) only")  # fmt: skip
     samples_by_group = _parse_groups(ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file)
     wanted = list(_wanted(samples_by_group, ploidy_config))
     if not any(names for _, names, _ in wanted):
         return {"outgroup": (None, None), **{group: (None, samples) for group, samples in samples_by_group.items()}}, None
     where = chr_name if start is None and end is None else f"{chr_name}:{start}-{end}"
     try:
-        pos, packed, n_matched, n_anc = plink.load_packed_device(eng, vcf_file, chr_name, [(names, ploidy) for _, names, ploidy in wanted],
-                                                                 start, end, anc_allele_file)  # fmt: skip
+        pos, packed, n_matched, n_anc = reader.load_packed_device(eng, vcf_file, chr_name, [(names, ploidy) for _, names, ploidy in wanted],
+                                                                  start, end, anc_allele_file)  # fmt: skip
     except FileNotFoundError:
         raise
     except Exception as e:  # utils.py:139-140

@@ -24,7 +24,7 @@ def build_library() -> None:
         _build.build()
         dst = ROOT / "sai_amd" / "include"
         dst.mkdir(exist_ok=True)
-        for header in ("saihip.h", "saihip_plink.h", "saihip_eigenstrat.h", "saihip_pgen.h", "saihip_packed_ingest.h"):
+        for header in ("saihip.h", "saihip_plink.h", "saihip_eigenstrat.h", "saihip_pgen.h", "saihip_packed_ingest.h", "saihip_pgen_packed.h"):
             shutil.copy2(ROOT / "include" / header, dst / header)  # travel as package data
     finally:
         sys.path.remove(str(ROOT))
