@@ -56,28 +56,10 @@ struct PackArgs {
   int32_t n_groups;        // n_full + (w_tail != 0)
 };
 
-// bit 2k set for every field k < n (any n: none below 1, all from 16 on)
-__device__ __forceinline__ uint32_t valid_fields(int n) {
-  return n >= 16 ? 0x55555555u : (n <= 0 ? 0u : (0x55555555u & ((1u << (2 * n)) - 1u)));
-}
-
-// the four words of group g of one site
-__device__ __forceinline__ void store_group(const PackArgs& a, uint32_t* out, int site_in_tile, int g, const u32x4& word) {
-  if (g < a.n_full) {
-    reinterpret_cast<u32x4*>(out)[g * kTile + site_in_tile] = word;
-  } else {
-    uint32_t* tw = out + static_cast<int64_t>(a.n_full) * 256 + site_in_tile * a.w_tail;
-    tw[0] = word[0];
-    if (a.w_tail > 1) tw[1] = word[1];
-    if (a.w_tail > 2) tw[2] = word[2];
-    if (a.w_tail > 3) tw[3] = word[3];
-  }
-}
-
 // every word of one site the same (a bad row: 0; a padding site: ones)
 __device__ __forceinline__ void fill_site(const PackArgs& a, uint32_t* out, int site_in_tile, uint32_t value) {
   const u32x4 word = {value, value, value, value};
-  for (int g = threadIdx.x; g < a.n_groups; g += kWave) store_group(a, out, site_in_tile, g, word);
+  for (int g = threadIdx.x; g < a.n_groups; g += kWave) packed2_store_group(out, a.n_full, a.w_tail, site_in_tile, g, word);
 }
 
 template <int PLOIDY, bool FAST>
@@ -129,7 +111,7 @@ __global__ __launch_bounds__(kWave) void pgen_pack2_kernel(PackArgs a) {
             if (PLOIDY == 1 && het && first_het < 0) first_het = 64 * g + 16 * j + (__builtin_ctz(het) >> 1);
             if (PLOIDY == 2 && unfit && first_unfit < 0) first_unfit = 64 * g + 16 * j + (__builtin_ctz(unfit) >> 1);
           }
-          store_group(a, out, sit, g, word);
+          packed2_store_group(out, a.n_full, a.w_tail, sit, g, word);
         }
         __syncthreads();  // the next window, or the next row, overwrites the codes
       }
@@ -176,7 +158,7 @@ __global__ __launch_bounds__(kWave) void pgen_pack2_kernel(PackArgs a) {
           if (PLOIDY == 1 && het && first_het < 0) first_het = 64 * g + 16 * j + (__builtin_ctz(het) >> 1);
           if (PLOIDY == 2 && unfit && first_unfit < 0) first_unfit = 64 * g + 16 * j + (__builtin_ctz(unfit) >> 1);
         }
-        store_group(a, out, sit, g, word);
+        packed2_store_group(out, a.n_full, a.w_tail, sit, g, word);
       }
       __syncthreads();  // the next row overwrites the codes
     }
@@ -199,11 +181,8 @@ extern "C" int sai_pgen_pack2(sai_ctx* ctx, const uint8_t* bytes, int64_t n_byte
                               const int32_t* col_of_ind, int32_t first_col, int32_t ploidy, uint8_t* packed, int64_t n_sites,
                               int64_t out_row0, int32_t* status, int32_t* unfit, void* stream) {
   if (int rc = enter(ctx)) return rc;
-  if (n_bytes < 0 || n_out_rows < 0 || sample_ct < 1 || n_ind < 1 || n_ind > kPackedMaxInd || out_row0 < 0 || n_sites < 0 ||
-      n_sites >= 0x7FFFFFFFll || out_row0 > n_sites || n_out_rows > n_sites - out_row0)
-    return fail(SAI_ERR_ARG, "size out of range");
-  if (ploidy != 1 && ploidy != 2) return fail(SAI_ERR_ARG, "ploidy must be 1 or 2");
-  if (first_col >= 0 && static_cast<int64_t>(first_col) + n_ind > sample_ct) return fail(SAI_ERR_ARG, "first_col + n_slots exceeds sample_ct");
+  if (n_bytes < 0 || sample_ct < 1 || !packed2_sizes_ok(n_out_rows, n_ind, n_sites, out_row0)) return fail(SAI_ERR_ARG, "size out of range");
+  if (const char* why = packed2_bad_selection(ploidy, first_col, n_ind, sample_ct, "first_col + n_slots exceeds sample_ct")) return fail(SAI_ERR_ARG, "%s", why);
   if (n_out_rows == 0) return SAI_OK;
   if (!rec || !base || !row_flip || !packed || !status || !unfit || (first_col < 0 && !col_of_ind) || (n_bytes > 0 && !bytes))
     return fail(SAI_ERR_ARG, "NULL buffer");
@@ -225,23 +204,11 @@ extern "C" int sai_pgen_pack2(sai_ctx* ctx, const uint8_t* bytes, int64_t n_byte
   a.n_pad = row_end == n_sites ? (kTile - row_end % kTile) % kTile : 0;
   a.status = status;
   a.unfit = unfit;
-  a.n_full = packed2_full_groups(n_ind);
-  a.w_tail = packed2_tail_words(n_ind);
-  a.n_groups = a.n_full + (a.w_tail ? 1 : 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  SAI_HIP(hipMemsetAsync(status, 0, static_cast<size_t>(n_out_rows) * sizeof(int32_t), st));
-  SAI_HIP(hipMemsetAsync(unfit, 0, static_cast<size_t>(n_out_rows) * sizeof(int32_t), st));
+  packed2_set_groups(a, n_ind);
   // a wavefront per row (and per padding site); beyond the 16 per CU that are resident at once rows are taken in a grid stride
   const int64_t want = n_out_rows + a.n_pad;
   const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;
   const dim3 grid(static_cast<unsigned>(want < cap ? want : cap)), block(kWave);
-  const bool fast = a.first_col >= 0;
-  if (ploidy == 2) {
-    if (fast) hipLaunchKernelGGL((pgen_pack2_kernel<2, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((pgen_pack2_kernel<2, false>), grid, block, 0, st, a);
-  } else {
-    if (fast) hipLaunchKernelGGL((pgen_pack2_kernel<1, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((pgen_pack2_kernel<1, false>), grid, block, 0, st, a);
-  }
+  SAI_PACKED2_LAUNCH(pgen_pack2_kernel, a, ploidy, n_out_rows, grid, block, stream);
   return check_launch("pgen_pack2");
 }

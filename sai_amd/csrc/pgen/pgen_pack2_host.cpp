@@ -23,25 +23,13 @@ int pgen_pack2_host_impl(const uint8_t* bytes, int64_t n_bytes, int64_t n_out_ro
                          const uint8_t* row_flip, int32_t sample_ct, int32_t n_ind, const int32_t* col_of_ind, int32_t first_col,
                          int32_t ploidy, uint8_t* packed, int64_t n_sites, int64_t out_row0, int32_t* status, int32_t* unfit,
                          int32_t n_threads) {
-  if (n_bytes < 0 || n_out_rows < 0 || sample_ct < 1 || n_ind < 1 || n_ind > kPackedMaxInd || out_row0 < 0 || n_sites < 0 ||
-      n_sites >= 0x7FFFFFFFll || out_row0 > n_sites || n_out_rows > n_sites - out_row0)
-    return sai_set_error(SAI_ERR_ARG, "size out of range");
-  if (ploidy != 1 && ploidy != 2) return sai_set_error(SAI_ERR_ARG, "ploidy must be 1 or 2");
-  if (first_col >= 0 && static_cast<int64_t>(first_col) + n_ind > sample_ct) return sai_set_error(SAI_ERR_ARG, "first_col + n_slots exceeds sample_ct");
+  if (n_bytes < 0 || sample_ct < 1 || !packed2_sizes_ok(n_out_rows, n_ind, n_sites, out_row0)) return sai_set_error(SAI_ERR_ARG, "size out of range");
+  if (const char* why = packed2_bad_selection(ploidy, first_col, n_ind, sample_ct, "first_col + n_slots exceeds sample_ct")) return sai_set_error(SAI_ERR_ARG, "%s", why);
   if (n_out_rows == 0) return SAI_OK;
   if (!rec || !base || !row_flip || !packed || !status || !unfit || (first_col < 0 && !col_of_ind) || (n_bytes > 0 && !bytes))
     return sai_set_error(SAI_ERR_ARG, "NULL buffer");
   const uint32_t n = static_cast<uint32_t>(sample_ct);
-  const int n_full = packed2_full_groups(n_ind), w_tail = packed2_tail_words(n_ind);
-  const int64_t tile_words = packed2_tile_words(n_ind);
-  const int words_per_site = n_full * 4 + w_tail;
-  // word j of a site (16 individuals from 16 * j on) inside its tile: full groups site-major, then the tail block
-  auto word_at = [&](int64_t site, int j) {
-    const int64_t tile = site / 64, s = site % 64;
-    const int64_t in_tile = j < n_full * 4 ? static_cast<int64_t>(j / 4) * 256 + s * 4 + j % 4
-                                           : static_cast<int64_t>(n_full) * 256 + s * w_tail + (j - n_full * 4);
-    return packed + (tile * tile_words + in_tile) * 4;
-  };
+  const Packed2Block block(packed, n_ind);
   std::atomic<bool> failed{false};
   auto decode = [&](int64_t lo, int64_t hi) {
     std::vector<uint8_t> codes;
@@ -57,7 +45,7 @@ int pgen_pack2_host_impl(const uint8_t* bytes, int64_t n_bytes, int64_t n_out_ro
       const bool sound = expand_record(bytes, n_bytes, own, from, n, codes.data());
       int32_t st = sound ? 0 : kPgenBadRecord, uf = 0;
       const uint8_t* table = kPgenPack2Table[ploidy - 1][row_flip[r] != 0];
-      for (int j = 0; j < words_per_site; ++j) {
+      for (int j = 0; j < block.words_per_site; ++j) {
         uint32_t word = 0;
         for (int k = 0; sound && k < 16; ++k) {  // a bad row: every field 0
           const int32_t i = j * 16 + k;
@@ -72,24 +60,16 @@ int pgen_pack2_host_impl(const uint8_t* bytes, int64_t n_bytes, int64_t n_out_ro
           else if (field == kPgenPack2Unfit) uf = std::max(uf, n_ind - i);
           else word |= static_cast<uint32_t>(field) << (2 * k);
         }
-        std::memcpy(word_at(out_row0 + r, j), &word, 4);
+        block.put(out_row0 + r, j, word);
       }
       status[r] = st;
       unfit[r] = uf;
     }
   };
   const int64_t cells = n_out_rows * (static_cast<int64_t>(n_ind) + sample_ct);
-  const int nt = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>({static_cast<int64_t>(std::max(n_threads, 1)), n_out_rows, cells / (int64_t(1) << 18) + 1})));
-  ThreadGroup tg;
-  for (int t = 1; t < nt; ++t) tg.spawn([&decode, t, nt, n_out_rows] { decode(n_out_rows * t / nt, n_out_rows * (t + 1) / nt); });
-  decode(0, n_out_rows / nt);
-  tg.join();
+  packed2_for_rows(n_threads, n_out_rows, cells, decode);
   if (failed) return sai_set_error(SAI_ERR_HIP, "out of host memory");
-  if (out_row0 + n_out_rows == n_sites) {  // the padding sites of the last tile: all missing
-    const uint32_t ones = 0xFFFFFFFFu;
-    for (int64_t site = n_sites; site % 64 != 0; ++site)
-      for (int j = 0; j < words_per_site; ++j) std::memcpy(word_at(site, j), &ones, 4);
-  }
+  block.pad(out_row0 + n_out_rows, n_sites);
   return SAI_OK;
 }
 

@@ -64,11 +64,6 @@ __device__ __forceinline__ uint32_t load_word(const PackArgs& a, const uint8_t* 
   return w;
 }
 
-// bit 2k set for every field k < n (any n: none below 1, all from 16 on)
-__device__ __forceinline__ uint32_t valid_fields(int n) {
-  return n >= 16 ? 0x55555555u : (n <= 0 ? 0u : (0x55555555u & ((1u << (2 * n)) - 1u)));
-}
-
 template <int PLOIDY, bool FAST>
 __global__ __launch_bounds__(kPackBlock) void bed_pack2_kernel(PackArgs a) {
   const int lane = threadIdx.x & 63;
@@ -146,15 +141,7 @@ __global__ __launch_bounds__(kPackBlock) void bed_pack2_kernel(PackArgs a) {
           if (PLOIDY == 2 && unfit && first_unfit < 0) first_unfit = 64 * g + 16 * j + (__builtin_ctz(unfit) >> 1);
         }
       }
-      if (g < a.n_full) {
-        reinterpret_cast<u32x4*>(out)[g * kTile + lane] = word;  // the group's 1 KiB block, one store per wave
-      } else {
-        uint32_t* tw = out + static_cast<int64_t>(a.n_full) * 256 + lane * a.w_tail;
-        tw[0] = word[0];
-        if (a.w_tail > 1) tw[1] = word[1];
-        if (a.w_tail > 2) tw[2] = word[2];
-        if (a.w_tail > 3) tw[3] = word[3];
-      }
+      packed2_store_group(out, a.n_full, a.w_tail, lane, g, word);  // a full group: its 1 KiB block, one store per wave
     }
     if (first_het >= 0) atomicMax(a.status + r, a.n_ind - first_het);
     if (first_unfit >= 0) atomicMax(a.unfit + r, a.n_ind - first_unfit);
@@ -177,12 +164,10 @@ extern "C" int sai_bed_pack2(sai_ctx* ctx, const uint8_t* rows, int64_t n_batch_
                              const int32_t* col_of_ind, int32_t first_col, int32_t ploidy, uint8_t* packed, int64_t n_sites,
                              int64_t out_row0, int32_t* status, int32_t* unfit, void* stream) {
   if (int rc = enter(ctx)) return rc;
-  if (n_batch_rows < 0 || row_bytes < 0 || n_out_rows < 0 || n_cols < 0 || n_ind < 1 || n_ind > kPackedMaxInd || out_row0 < 0 ||
-      n_sites < 0 || n_sites >= 0x7FFFFFFFll || out_row0 > n_sites || n_out_rows > n_sites - out_row0)
+  if (n_batch_rows < 0 || row_bytes < 0 || n_cols < 0 || !packed2_sizes_ok(n_out_rows, n_ind, n_sites, out_row0))
     return fail(SAI_ERR_ARG, "size out of range");
   if (static_cast<int64_t>(n_cols) > 4 * row_bytes) return fail(SAI_ERR_ARG, "n_cols exceeds the 4 * row_bytes genotypes of a row");
-  if (ploidy != 1 && ploidy != 2) return fail(SAI_ERR_ARG, "ploidy must be 1 or 2");
-  if (first_col >= 0 && static_cast<int64_t>(first_col) + n_ind > n_cols) return fail(SAI_ERR_ARG, "first_col + n_slots exceeds n_cols");
+  if (const char* why = packed2_bad_selection(ploidy, first_col, n_ind, n_cols, "first_col + n_slots exceeds n_cols")) return fail(SAI_ERR_ARG, "%s", why);
   if (n_out_rows == 0) return SAI_OK;
   if (!row_in_batch || !row_flip || !packed || !status || !unfit || (first_col < 0 && !col_of_ind) ||
       (n_batch_rows > 0 && row_bytes > 0 && !rows))
@@ -206,28 +191,16 @@ extern "C" int sai_bed_pack2(sai_ctx* ctx, const uint8_t* rows, int64_t n_batch_
   a.row_end = out_row0 + n_out_rows;
   a.status = status;
   a.unfit = unfit;
-  a.n_full = packed2_full_groups(n_ind);
-  a.w_tail = packed2_tail_words(n_ind);
-  a.n_groups = a.n_full + (a.w_tail ? 1 : 0);
+  packed2_set_groups(a, n_ind);
   a.groups_per_run = groups_per_run();
   a.runs_per_tile = (a.n_groups + a.groups_per_run - 1) / a.groups_per_run;
   a.tile0 = out_row0 / kTile;
   const int64_t n_tiles = (a.row_end + kTile - 1) / kTile - a.tile0;
   a.n_units = n_tiles * a.runs_per_tile;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  SAI_HIP(hipMemsetAsync(status, 0, static_cast<size_t>(n_out_rows) * sizeof(int32_t), st));
-  SAI_HIP(hipMemsetAsync(unfit, 0, static_cast<size_t>(n_out_rows) * sizeof(int32_t), st));
   // a memory-bound pass: enough workgroups to fill the chip, grid-stride beyond that
   const int64_t want = (a.n_units + kPackBlock / 64 - 1) / (kPackBlock / 64);
   const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;
   const dim3 grid(static_cast<unsigned>(want < cap ? want : cap)), block(kPackBlock);
-  const bool fast = a.first_col >= 0;
-  if (ploidy == 2) {
-    if (fast) hipLaunchKernelGGL((bed_pack2_kernel<2, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((bed_pack2_kernel<2, false>), grid, block, 0, st, a);
-  } else {
-    if (fast) hipLaunchKernelGGL((bed_pack2_kernel<1, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((bed_pack2_kernel<1, false>), grid, block, 0, st, a);
-  }
+  SAI_PACKED2_LAUNCH(bed_pack2_kernel, a, ploidy, n_out_rows, grid, block, stream);
   return check_launch("bed_pack2");
 }

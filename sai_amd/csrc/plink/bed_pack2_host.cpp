@@ -20,26 +20,15 @@ int bed_pack2_host_impl(const uint8_t* rows, int64_t n_batch_rows, int64_t row_b
                         const int32_t* row_in_batch, const uint8_t* row_flip, int32_t n_cols, int32_t n_ind,
                         const int32_t* col_of_ind, int32_t first_col, int32_t ploidy, uint8_t* packed, int64_t n_sites,
                         int64_t out_row0, int32_t* status, int32_t* unfit, int32_t n_threads) {
-  if (n_batch_rows < 0 || row_bytes < 0 || n_out_rows < 0 || n_cols < 0 || n_ind < 1 || n_ind > kPackedMaxInd || out_row0 < 0 ||
-      n_sites < 0 || n_sites >= 0x7FFFFFFFll || out_row0 > n_sites || n_out_rows > n_sites - out_row0)
+  if (n_batch_rows < 0 || row_bytes < 0 || n_cols < 0 || !packed2_sizes_ok(n_out_rows, n_ind, n_sites, out_row0))
     return sai_set_error(SAI_ERR_ARG, "size out of range");
   if (static_cast<int64_t>(n_cols) > 4 * row_bytes) return sai_set_error(SAI_ERR_ARG, "n_cols exceeds the 4 * row_bytes genotypes of a row");
-  if (ploidy != 1 && ploidy != 2) return sai_set_error(SAI_ERR_ARG, "ploidy must be 1 or 2");
-  if (first_col >= 0 && static_cast<int64_t>(first_col) + n_ind > n_cols) return sai_set_error(SAI_ERR_ARG, "first_col + n_slots exceeds n_cols");
+  if (const char* why = packed2_bad_selection(ploidy, first_col, n_ind, n_cols, "first_col + n_slots exceeds n_cols")) return sai_set_error(SAI_ERR_ARG, "%s", why);
   if (n_out_rows == 0) return SAI_OK;
   if (!row_in_batch || !row_flip || !packed || !status || !unfit || (first_col < 0 && !col_of_ind) ||
       (n_batch_rows > 0 && row_bytes > 0 && !rows))
     return sai_set_error(SAI_ERR_ARG, "NULL buffer");
-  const int n_full = packed2_full_groups(n_ind), w_tail = packed2_tail_words(n_ind);
-  const int64_t tile_words = packed2_tile_words(n_ind);
-  const int words_per_site = n_full * 4 + w_tail;
-  // word j of a site (16 individuals from 16 * j on) inside its tile: full groups site-major, then the tail block
-  auto word_at = [&](int64_t site, int j) {
-    const int64_t tile = site / 64, s = site % 64;
-    const int64_t in_tile = j < n_full * 4 ? static_cast<int64_t>(j / 4) * 256 + s * 4 + j % 4
-                                           : static_cast<int64_t>(n_full) * 256 + s * w_tail + (j - n_full * 4);
-    return packed + (tile * tile_words + in_tile) * 4;
-  };
+  const Packed2Block block(packed, n_ind);
   auto decode = [&](int64_t lo, int64_t hi) {
     for (int64_t r = lo; r < hi; ++r) {
       int32_t st = 0, uf = 0;
@@ -47,7 +36,7 @@ int bed_pack2_host_impl(const uint8_t* rows, int64_t n_batch_rows, int64_t row_b
       const bool row_ok = rib >= 0 && rib < n_batch_rows;
       const uint8_t* src = row_ok ? rows + rib * row_bytes : nullptr;
       const uint8_t* table = kPack2Table[ploidy - 1][row_flip[r] != 0];
-      for (int j = 0; j < words_per_site; ++j) {
+      for (int j = 0; j < block.words_per_site; ++j) {
         uint32_t word = 0;
         for (int k = 0; k < 16; ++k) {
           const int32_t i = j * 16 + k;
@@ -62,23 +51,15 @@ int bed_pack2_host_impl(const uint8_t* rows, int64_t n_batch_rows, int64_t row_b
           else if (field == kPack2Unfit) uf = std::max(uf, n_ind - i);
           else word |= static_cast<uint32_t>(field) << (2 * k);
         }
-        std::memcpy(word_at(out_row0 + r, j), &word, 4);
+        block.put(out_row0 + r, j, word);
       }
       status[r] = st;
       unfit[r] = uf;
     }
   };
   const int64_t cells = n_out_rows * static_cast<int64_t>(n_ind);
-  const int nt = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>({static_cast<int64_t>(std::max(n_threads, 1)), n_out_rows, cells / (int64_t(1) << 18) + 1})));
-  ThreadGroup tg;
-  for (int t = 1; t < nt; ++t) tg.spawn([&decode, t, nt, n_out_rows] { decode(n_out_rows * t / nt, n_out_rows * (t + 1) / nt); });
-  decode(0, n_out_rows / nt);
-  tg.join();
-  if (out_row0 + n_out_rows == n_sites) {  // the padding sites of the last tile: all missing
-    const uint32_t ones = 0xFFFFFFFFu;
-    for (int64_t site = n_sites; site % 64 != 0; ++site)
-      for (int j = 0; j < words_per_site; ++j) std::memcpy(word_at(site, j), &ones, 4);
-  }
+  packed2_for_rows(n_threads, n_out_rows, cells, decode);
+  block.pad(out_row0 + n_out_rows, n_sites);
   return SAI_OK;
 }
 

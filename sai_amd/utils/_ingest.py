@@ -1,8 +1,9 @@
 """The steps the ingest readers share (``native_vcf``, ``device_vcf``, ``plink``, ``eigenstrat``, ``pgen``): the region /
 sample arguments of the C ABI, its errors as ValueError, the staging kept on the engine, the batches and the
 ``pread`` of fixed-length rows (the PLINK 1 and EIGENSOFT readers) and of variable-length records (the PLINK 2
-reader), and -- ``Records`` -- what the two GPU-tokenising VCF
-routes do with the record lines of a batch."""
+reader), the loop of the fileset readers over those batches -- ``read_batches`` on the host, ``staged_copy`` through
+two pinned buffers and a side stream to the device -- and, ``Records``, what the two GPU-tokenising VCF routes do with
+the record lines of a batch."""
 
 from __future__ import annotations
 
@@ -203,6 +204,83 @@ def pread_into(fd: int, view: memoryview, reads, path: str) -> None:
     else:
         for piece in pieces:
             one(piece)
+
+
+def read_batches(path: str, batches, decode) -> None:
+    """The host readers' loop: every batch ``(reads, nbytes, item)`` of ``batches`` is ``pread`` from ``path`` into
+    one buffer that grows to the largest of them, and ``decode(buf, item)`` takes it from there."""
+    buf = None
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        for reads, nbytes, item in batches:
+            if buf is None or buf.size < nbytes:
+                buf = np.empty(nbytes, dtype=np.uint8)
+            pread_into(fd, memoryview(buf), reads, path)
+            decode(buf, item)
+    finally:
+        os.close(fd)
+
+
+def staged_copy(eng, key: str, size: int, path: str, batches, launch, trace=None, counter: str = ""):
+    """The device readers' loop.  Every batch ``(reads, nbytes, item)`` of ``batches`` is ``pread`` from ``path`` into
+    two pinned buffers of ``size`` bytes in turn and copied to their device twins on a side stream; behind the copy
+    ``launch(device pointer of the batch's bytes, item, side stream)`` enqueues the batch's tables and kernels, inside
+    the side-stream context, so the file read of batch k + 1 runs under the copy and the kernels of batch k.  The
+    buffers and the stream are kept on the engine under ``key`` for the next call.  Returns the side stream, drained:
+    the caller looks at its flags and lets the current stream wait for it.
+
+    ``launch`` returns the device tensors that must outlive it (the batch's tables).  They are held per buffer and
+    those of two batches back go: they are allocated and used on the side stream alone, so the caching allocator
+    hands their memory to nothing that could run before the kernels that read them.
+
+    ``trace`` (a dict) collects host-clock seconds per phase: always ``file_read``, and under ``counter`` the bytes
+    read; with ``trace["serial"]`` set the side stream is synchronised behind every copy and every ``launch``, so
+    ``h2d`` and ``decode`` are timed on their own (and nothing overlaps)."""
+    import itertools
+    import time
+
+    import torch
+
+    batches = iter(batches)
+    head = list(itertools.islice(batches, 1))  # a buffer that is too small is refused here, before anything is page-locked
+    st = staging(eng, key, size, lambda: {"pinned": pair(size), "rows": pair(size, device=eng.device),
+                                          "stream": torch.cuda.Stream(device=eng.device)})  # fmt: skip
+    pinned, dev_rows, side = st["pinned"], st["rows"], st["stream"]
+    copied = [None, None]  # per buffer: the event behind its last H2D copy
+    tables = [None, None]  # per buffer: what the ``launch`` of its last batch returned
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        side.wait_stream(torch.cuda.current_stream(eng.device))  # the caller's outputs were allocated on the current stream
+        b = 0
+        for reads, nbytes, item in itertools.chain(head, batches):
+            if copied[b] is not None:
+                copied[b].synchronize()  # the copy two batches back has left this pinned buffer
+            t1 = time.perf_counter()
+            pread_into(fd, memoryview(pinned[b].numpy()), reads, path)
+            if trace is not None:
+                trace["file_read"] = trace.get("file_read", 0.0) + time.perf_counter() - t1
+                # the bytes read, not the bytes staged: the same for row_batches ((hi - lo) rows, in ranges back to back)
+                # and span_batches (front + hi - lo), fewer where the reads lie apart in the buffer (a padded stride)
+                trace[counter] += sum(r[2] for r in reads)
+            serial = trace is not None and trace.get("serial")
+            with torch.cuda.stream(side):
+                t1 = time.perf_counter()
+                dev_rows[b][:nbytes].copy_(pinned[b][:nbytes], non_blocking=True)
+                copied[b] = torch.cuda.Event()
+                copied[b].record(side)
+                if serial:
+                    side.synchronize()
+                    trace["h2d"] = trace.get("h2d", 0.0) + time.perf_counter() - t1
+                    t1 = time.perf_counter()
+                tables[b] = launch(dev_rows[b].data_ptr(), item, side)
+                if serial:
+                    side.synchronize()
+                    trace["decode"] = trace.get("decode", 0.0) + time.perf_counter() - t1
+            b ^= 1
+    finally:
+        os.close(fd)
+        side.synchronize()  # also on an error: the staging buffers are reused by the next call
+    return side
 
 
 class Records:

@@ -28,7 +28,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .. import _ffi, _ffi_eigenstrat
-from ._ingest import check_io, default_threads, pair, pread_into, region_args, row_batches, staging
+from ._ingest import check_io, default_threads, read_batches, region_args, row_batches, staged_copy
 
 BUFFER_BYTES = 32 << 20  # as the other routes; SAI_AMD_INGEST_BUFFER overrides it
 _EXTENSIONS = (".geno", ".snp", ".ind")
@@ -160,7 +160,8 @@ class _Index:
             size = os.path.getsize(self.geno)  # the last line of a text file may lack its newline
             for k0, k1, rib, n_batch_rows, reads in row_batches(self.file_row, self.record_bytes, self.data_offset, cap,
                                                                 _READ_THROUGH_BYTES, self.geno, self.prefix + ".snp"):  # fmt: skip
-                reads = [(at, off, min(n, size - off)) for at, off, n in reads]
+                if self.encoding == TEXT:  # a packed file has the size the index checked: one that ends early since is a read error
+                    reads = [(at, off, min(n, size - off)) for at, off, n in reads]
                 yield _Batch(k0, k1, rib, n_batch_rows, reads, n_batch_rows * self.record_bytes, self.record_bytes)
             return
         n_staged = self.n_cols
@@ -180,6 +181,10 @@ class _Index:
             reads = [(d * stride, self.data_offset + int(line) * self.record_bytes + b0, b1 - b0) for d, line in enumerate(self.staged_lines)]
             yield _Batch(k0, k1, (self.file_row[k0:k1] - s0).astype(np.int32), s1 - s0, reads, n_staged * stride, stride, s0 & 3)
             k0 = k1
+
+    def staged(self, cap: int):
+        """``batches`` as the shared loops take them: ``(reads, bytes staged, batch)``."""
+        return ((bt.reads, bt.nbytes, bt) for bt in self.batches(cap))
 
     def raise_flagged(self, status: np.ndarray, row0: int = 0) -> None:
         """The first flagged row of ``status`` (rows ``row0 ..`` of the index) as the reader's ValueError."""
@@ -231,26 +236,18 @@ def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[
     dos = np.empty((idx.n_rows, n), dtype=np.int8)
     if n == 0 or idx.n_rows == 0:
         return idx.pos, dos, idx.n_matched, idx.n_anc
-    cap = _cap(buffer_bytes)
     status = np.empty(idx.n_rows, dtype=np.int32)
-    cols = idx.cols
-    buf = None
-    fd = os.open(idx.geno, os.O_RDONLY)
-    try:
-        for bt in idx.batches(cap):
-            if buf is None or buf.size < bt.nbytes:
-                buf = np.empty(bt.nbytes, dtype=np.uint8)
-            pread_into(fd, memoryview(buf), bt.reads, idx.geno)
-            if bt.k1 == bt.k0:
-                continue
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+
+    def decode(buf, bt):
+        if bt.k1 > bt.k0:
             check_io(lib, lib.sai_eigenstrat_decode_host(
-                idx.encoding, buf.ctypes.data_as(C.c_void_p), bt.n_batch, bt.stride, bt.first_code, bt.k1 - bt.k0,
-                bt.row_in_batch.ctypes.data_as(C.c_void_p), idx.flip[bt.k0 : bt.k1].ctypes.data_as(C.c_void_p), idx.n_cols, n,
-                cols.ctypes.data_as(C.c_void_p), idx.ploidies.ctypes.data_as(C.c_void_p), dos[bt.k0 : bt.k1].ctypes.data_as(C.c_void_p),
-                status[bt.k0 : bt.k1].ctypes.data_as(C.c_void_p), n_threads,
+                idx.encoding, ptr(buf), bt.n_batch, bt.stride, bt.first_code, bt.k1 - bt.k0, ptr(bt.row_in_batch),
+                ptr(idx.flip[bt.k0 : bt.k1]), idx.n_cols, n, ptr(idx.cols), ptr(idx.ploidies), ptr(dos[bt.k0 : bt.k1]),
+                ptr(status[bt.k0 : bt.k1]), n_threads,
             ))  # fmt: skip
-    finally:
-        os.close(fd)
+
+    read_batches(idx.geno, idx.staged(_cap(buffer_bytes)), decode)
     idx.raise_flagged(status)
     return idx.pos, dos, idx.n_matched, idx.n_anc
 
@@ -268,10 +265,10 @@ def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidie
                        n_threads: Optional[int] = None, buffer_bytes: Optional[int] = None, trace: Optional[dict] = None):  # fmt: skip
     """(pos int32 host array [n], dosage int8 DEVICE tensor [n][len(samples)], n_matched, n_anc_entries):
     ``load_dosage`` with the result left in HBM.  The bytes of a batch are ``pread`` into two pinned buffers in
-    turn, copied on a side stream and decoded behind the copy, so the file read of batch k + 1 runs under the
-    copy and the kernel of batch k.  ``trace`` (a dict) collects host-clock seconds per phase: always ``index``
-    and ``file_read``; with ``trace["serial"]`` set the side stream is synchronised behind every copy and every
-    kernel, so ``h2d`` and ``decode`` are timed on their own (and nothing overlaps)."""
+    turn, copied on a side stream and decoded behind the copy (``_ingest.staged_copy``), so the file read of batch
+    k + 1 runs under the copy and the kernel of batch k.  ``trace`` (a dict) collects host-clock seconds per phase:
+    always ``index`` and ``file_read``; with ``trace["serial"]`` set the side stream is synchronised behind every copy
+    and every kernel, so ``h2d`` and ``decode`` are timed on their own (and nothing overlaps)."""
     import time
 
     import torch
@@ -289,72 +286,33 @@ def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidie
     if n == 0 or idx.n_rows == 0:
         return idx.pos, dos, idx.n_matched, idx.n_anc
     cap = _cap(buffer_bytes)
-    plan = idx.batches(cap)
-    first = next(plan)  # a buffer that is too small is refused before anything is page-locked
-    # two pinned staging buffers, their device twins and the side stream, kept for the next call
-    size = idx.staging_bytes(cap)
-    st = staging(eng, "_eigenstrat_state", size, lambda: {"pinned": pair(size), "rows": pair(size, device=eng.device),
-                                                          "stream": torch.cuda.Stream(device=eng.device)})  # fmt: skip
-    pinned, dev_rows, side = st["pinned"], st["rows"], st["stream"]
     status = torch.empty((idx.n_rows,), dtype=torch.int32, device=eng.device)
     cols_dev = None if idx.first_col >= 0 else torch.from_numpy(idx.cols).to(eng.device)
     ploidy_dev = None if idx.uniform_ploidy > 0 else torch.from_numpy(idx.ploidies).to(eng.device)
-    copied = [None, None]  # per buffer: the event behind its last H2D copy
-    keep = []
-    fd = os.open(idx.geno, os.O_RDONLY)
-    try:
-        side.wait_stream(torch.cuda.current_stream(eng.device))  # `dos` and `status` were allocated on the current stream
-        b = 0
 
-        def batches():
-            yield first
-            yield from plan
+    def launch(rows, bt, side):
+        if bt.k1 == bt.k0:
+            return None
+        d_rib = torch.from_numpy(bt.row_in_batch).to(eng.device, non_blocking=True)
+        d_flip = torch.from_numpy(idx.flip[bt.k0 : bt.k1]).to(eng.device, non_blocking=True)
+        out_ptr, status_ptr = C.c_void_p(dos.data_ptr()), C.c_void_p(status.data_ptr() + 4 * bt.k0)
+        stream_ptr, rows_ptr = C.c_void_p(side.cuda_stream), C.c_void_p(rows)
+        if idx.transposed:
+            _ffi.check(
+                lib.sai_eigenstrat_decode_transposed(eng.ctx, rows_ptr, idx.n_cols, bt.stride, bt.first_code, bt.n_batch, bt.k1 - bt.k0,
+                                                     eng._ptr(d_rib), eng._ptr(d_flip), n, eng._ptr(cols_dev), eng._ptr(ploidy_dev),
+                                                     out_ptr, bt.k0, status_ptr, stream_ptr)
+            )  # fmt: skip
+        else:
+            _ffi.check(
+                lib.sai_eigenstrat_decode(eng.ctx, idx.encoding, rows_ptr, bt.n_batch, bt.stride, bt.k1 - bt.k0, eng._ptr(d_rib),
+                                          eng._ptr(d_flip), idx.n_cols, n, eng._ptr(cols_dev), idx.first_col, eng._ptr(ploidy_dev),
+                                          idx.uniform_ploidy, out_ptr, bt.k0, status_ptr, stream_ptr)
+            )  # fmt: skip
+        return d_rib, d_flip
 
-        for bt in batches():
-            if copied[b] is not None:
-                copied[b].synchronize()  # the copy two batches back has left this pinned buffer
-            t1 = time.perf_counter()
-            pread_into(fd, memoryview(pinned[b].numpy()), bt.reads, idx.geno)
-            if trace is not None:
-                trace["file_read"] = trace.get("file_read", 0.0) + time.perf_counter() - t1
-                trace["geno_bytes"] += sum(r[2] for r in bt.reads)
-            serial = trace is not None and trace.get("serial")
-            with torch.cuda.stream(side):
-                t1 = time.perf_counter()
-                dev_rows[b][: bt.nbytes].copy_(pinned[b][: bt.nbytes], non_blocking=True)
-                copied[b] = torch.cuda.Event()
-                copied[b].record(side)
-                if serial:
-                    side.synchronize()
-                    trace["h2d"] = trace.get("h2d", 0.0) + time.perf_counter() - t1
-                    t1 = time.perf_counter()
-                if bt.k1 > bt.k0:
-                    d_rib = torch.from_numpy(bt.row_in_batch).to(eng.device, non_blocking=True)
-                    d_flip = torch.from_numpy(idx.flip[bt.k0 : bt.k1]).to(eng.device, non_blocking=True)
-                    keep.append((d_rib, d_flip))
-                    out_ptr, status_ptr = C.c_void_p(dos.data_ptr()), C.c_void_p(status.data_ptr() + 4 * bt.k0)
-                    stream_ptr, rows_ptr = C.c_void_p(side.cuda_stream), C.c_void_p(dev_rows[b].data_ptr())
-                    if idx.transposed:
-                        _ffi.check(
-                            lib.sai_eigenstrat_decode_transposed(eng.ctx, rows_ptr, idx.n_cols, bt.stride, bt.first_code, bt.n_batch,
-                                                                 bt.k1 - bt.k0, eng._ptr(d_rib), eng._ptr(d_flip), n, eng._ptr(cols_dev),
-                                                                 eng._ptr(ploidy_dev), out_ptr, bt.k0, status_ptr, stream_ptr)
-                        )  # fmt: skip
-                    else:
-                        _ffi.check(
-                            lib.sai_eigenstrat_decode(eng.ctx, idx.encoding, rows_ptr, bt.n_batch, bt.stride, bt.k1 - bt.k0,
-                                                      eng._ptr(d_rib), eng._ptr(d_flip), idx.n_cols, n, eng._ptr(cols_dev), idx.first_col,
-                                                      eng._ptr(ploidy_dev), idx.uniform_ploidy, out_ptr, bt.k0, status_ptr, stream_ptr)
-                        )  # fmt: skip
-                if serial:
-                    side.synchronize()
-                    trace["decode"] = trace.get("decode", 0.0) + time.perf_counter() - t1
-            b ^= 1
-    finally:
-        os.close(fd)
-        side.synchronize()  # also on an error: the staging buffers are reused by the next call
-    flagged = status.cpu().numpy() if bool(status.any()) else None
-    if flagged is not None:
-        idx.raise_flagged(flagged)
+    side = staged_copy(eng, "_eigenstrat_state", idx.staging_bytes(cap), idx.geno, idx.staged(cap), launch, trace, "geno_bytes")
+    if bool(status.any()):
+        idx.raise_flagged(status.cpu().numpy())
     torch.cuda.current_stream(eng.device).wait_stream(side)
     return idx.pos, dos, idx.n_matched, idx.n_anc

@@ -27,7 +27,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .. import _ffi, _ffi_packed_ingest, _ffi_plink
-from ._ingest import check_io, default_threads, pair, pread_into, region_args, row_batches, staging
+from ._ingest import check_io, default_threads, read_batches, region_args, row_batches, staged_copy
+from ._packed import _PackedPlan, _packed_bytes
 
 BUFFER_BYTES = 32 << 20  # as the VCF route (device_vcf.BUFFER_BYTES); SAI_AMD_INGEST_BUFFER overrides it
 _MAGIC = b"\x6c\x1b"
@@ -114,6 +115,10 @@ class _Index:
         file offset, bytes)]."""
         return row_batches(self.file_row, self.row_bytes, 3, cap, _READ_THROUGH_BYTES, f"{self.prefix}.bed", f"{self.prefix}.bim")
 
+    def staged(self, cap: int):
+        """``batches`` as the shared loops take them: ``(reads, bytes staged, batch)``."""
+        return ((bt[4], bt[3] * self.row_bytes, bt) for bt in self.batches(cap))
+
     def raise_flagged(self, status: np.ndarray, row0: int = 0) -> None:
         """The first flagged row of ``status`` (rows ``row0 ..`` of the index) as the reader's ValueError."""
         bad = np.flatnonzero(status)
@@ -145,6 +150,10 @@ def _variant_id(prefix: str, file_row: int) -> str:
     return f"#{file_row + 1}"
 
 
+def _cap(buffer_bytes) -> int:
+    return int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
+
+
 def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[int], start: Optional[int] = None,
                 end: Optional[int] = None, anc_allele_file: Optional[str] = None, n_threads: Optional[int] = None,
                 buffer_bytes: Optional[int] = None):  # fmt: skip
@@ -157,27 +166,18 @@ def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[
     dos = np.empty((idx.n_rows, n), dtype=np.int8)
     if n == 0 or idx.n_rows == 0:
         return idx.pos, dos, idx.n_matched, idx.n_anc
-    cap = int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
     status = np.empty(idx.n_rows, dtype=np.int32)
-    flip = idx.flip
-    buf = None
-    fd = os.open(idx.prefix + ".bed", os.O_RDONLY)
-    try:
-        for k0, k1, rib, n_batch_rows, reads in idx.batches(cap):
-            nbytes = n_batch_rows * idx.row_bytes
-            if buf is None or buf.size < nbytes:
-                buf = np.empty(nbytes, dtype=np.uint8)
-            pread_into(fd, memoryview(buf), reads, idx.prefix + ".bed")
-            if k1 == k0:
-                continue
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+
+    def decode(buf, batch):
+        k0, k1, rib, n_batch_rows, _ = batch
+        if k1 > k0:
             check_io(lib, lib.sai_plink_decode_host(
-                buf.ctypes.data_as(C.c_void_p), n_batch_rows, idx.row_bytes, k1 - k0, rib.ctypes.data_as(C.c_void_p),
-                flip[k0:k1].ctypes.data_as(C.c_void_p), idx.n_fam, n, idx.col_of_slot.ctypes.data_as(C.c_void_p),
-                idx.ploidies.ctypes.data_as(C.c_void_p), dos[k0:k1].ctypes.data_as(C.c_void_p),
-                status[k0:k1].ctypes.data_as(C.c_void_p), n_threads,
+                ptr(buf), n_batch_rows, idx.row_bytes, k1 - k0, ptr(rib), ptr(idx.flip[k0:k1]), idx.n_fam, n, ptr(idx.col_of_slot),
+                ptr(idx.ploidies), ptr(dos[k0:k1]), ptr(status[k0:k1]), n_threads,
             ))  # fmt: skip
-    finally:
-        os.close(fd)
+
+    read_batches(idx.prefix + ".bed", idx.staged(_cap(buffer_bytes)), decode)
     idx.raise_flagged(status)
     return idx.pos, dos, idx.n_matched, idx.n_anc
 
@@ -195,10 +195,10 @@ def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidie
                        n_threads: Optional[int] = None, buffer_bytes: Optional[int] = None, trace: Optional[dict] = None):  # fmt: skip
     """(pos int32 host array [n], dosage int8 DEVICE tensor [n][len(samples)], n_matched, n_anc_entries):
     ``load_dosage`` with the result left in HBM.  The selected rows are ``pread`` into two pinned buffers in
-    turn, copied on a side stream and decoded behind the copy, so the file read of batch k + 1 runs under
-    the copy and the kernel of batch k.  ``trace`` (a dict) collects host-clock seconds per phase: always
-    ``index`` and ``file_read``; with ``trace["serial"]`` set the side stream is synchronised behind every
-    copy and every kernel, so ``h2d`` and ``decode`` are timed on their own (and nothing overlaps)."""
+    turn, copied on a side stream and decoded behind the copy (``_ingest.staged_copy``), so the file read of
+    batch k + 1 runs under the copy and the kernel of batch k.  ``trace`` (a dict) collects host-clock seconds per
+    phase: always ``index`` and ``file_read``; with ``trace["serial"]`` set the side stream is synchronised behind
+    every copy and every kernel, so ``h2d`` and ``decode`` are timed on their own (and nothing overlaps)."""
     import time
 
     import torch
@@ -214,116 +214,37 @@ def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidie
     dos = torch.empty((idx.n_rows, n), dtype=torch.int8, device=eng.device)
     if n == 0 or idx.n_rows == 0:
         return idx.pos, dos, idx.n_matched, idx.n_anc
-    cap = int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
-    plan = idx.batches(cap)
-    first = next(plan)  # a buffer smaller than one row is refused before anything is page-locked
-    # two pinned staging buffers, their device twins and the side stream, kept for the next call
-    st = staging(eng, "_plink_state", cap, lambda: {"pinned": pair(cap), "rows": pair(cap, device=eng.device),
-                                                    "stream": torch.cuda.Stream(device=eng.device)})  # fmt: skip
-    pinned, dev_rows, side = st["pinned"], st["rows"], st["stream"]
+    cap = _cap(buffer_bytes)
     status = torch.empty((idx.n_rows,), dtype=torch.int32, device=eng.device)
     cols_dev = None if idx.first_col >= 0 else torch.from_numpy(idx.col_of_slot).to(eng.device)
     ploidy_dev = None if idx.uniform_ploidy else torch.from_numpy(idx.ploidies).to(eng.device)
-    copied = [None, None]  # per buffer: the event behind its last H2D copy
-    keep = []
-    fd = os.open(idx.prefix + ".bed", os.O_RDONLY)
-    try:
-        side.wait_stream(torch.cuda.current_stream(eng.device))  # `dos` and `status` were allocated on the current stream
-        b = 0
 
-        def batches():
-            yield first
-            yield from plan
+    def launch(rows_ptr, batch, side):
+        k0, k1, rib, n_batch_rows, _ = batch
+        if k1 == k0:
+            return None
+        d_rib = torch.from_numpy(rib).to(eng.device, non_blocking=True)
+        d_flip = torch.from_numpy(idx.flip[k0:k1]).to(eng.device, non_blocking=True)
+        _ffi.check(
+            lib.sai_plink_decode(eng.ctx, C.c_void_p(rows_ptr), n_batch_rows, idx.row_bytes, k1 - k0, eng._ptr(d_rib), eng._ptr(d_flip),
+                                 idx.n_fam, n, eng._ptr(cols_dev), idx.first_col, eng._ptr(ploidy_dev), idx.uniform_ploidy,
+                                 C.c_void_p(dos.data_ptr()), k0, C.c_void_p(status.data_ptr() + 4 * k0), C.c_void_p(side.cuda_stream))
+        )  # fmt: skip
+        return d_rib, d_flip
 
-        for k0, k1, rib, n_batch_rows, reads in batches():
-            nbytes = n_batch_rows * idx.row_bytes
-            if copied[b] is not None:
-                copied[b].synchronize()  # the copy two batches back has left this pinned buffer
-            t1 = time.perf_counter()
-            pread_into(fd, memoryview(pinned[b].numpy()), reads, idx.prefix + ".bed")
-            if trace is not None:
-                trace["file_read"] = trace.get("file_read", 0.0) + time.perf_counter() - t1
-                trace["bed_bytes"] += nbytes
-            serial = trace is not None and trace.get("serial")
-            with torch.cuda.stream(side):
-                t1 = time.perf_counter()
-                dev_rows[b][:nbytes].copy_(pinned[b][:nbytes], non_blocking=True)
-                copied[b] = torch.cuda.Event()
-                copied[b].record(side)
-                if serial:
-                    side.synchronize()
-                    trace["h2d"] = trace.get("h2d", 0.0) + time.perf_counter() - t1
-                    t1 = time.perf_counter()
-                if k1 > k0:
-                    d_rib = torch.from_numpy(rib).to(eng.device, non_blocking=True)
-                    d_flip = torch.from_numpy(idx.flip[k0:k1]).to(eng.device, non_blocking=True)
-                    keep.append((d_rib, d_flip))
-                    _ffi.check(
-                        lib.sai_plink_decode(eng.ctx, C.c_void_p(dev_rows[b].data_ptr()), n_batch_rows, idx.row_bytes, k1 - k0,
-                                             eng._ptr(d_rib), eng._ptr(d_flip), idx.n_fam, n, eng._ptr(cols_dev), idx.first_col,
-                                             eng._ptr(ploidy_dev), idx.uniform_ploidy, C.c_void_p(dos.data_ptr()), k0,
-                                             C.c_void_p(status.data_ptr() + 4 * k0), C.c_void_p(side.cuda_stream))
-                    )  # fmt: skip
-                if serial:
-                    side.synchronize()
-                    trace["decode"] = trace.get("decode", 0.0) + time.perf_counter() - t1
-            b ^= 1
-    finally:
-        os.close(fd)
-        side.synchronize()  # also on an error: the staging buffers are reused by the next call
-    flagged = status.cpu().numpy() if bool(status.any()) else None
-    if flagged is not None:
-        idx.raise_flagged(flagged)
+    side = staged_copy(eng, "_plink_state", cap, idx.prefix + ".bed", idx.staged(cap), launch, trace, "bed_bytes")
+    if bool(status.any()):
+        idx.raise_flagged(status.cpu().numpy())
     torch.cuda.current_stream(eng.device).wait_stream(side)
     return idx.pos, dos, idx.n_matched, idx.n_anc
 
 
-class _PackedPlan:
-    """The populations of a packed read as slices of ONE index: population p holds the slots [lo, hi) of it, at one
-    ploidy, and ``first_col`` >= 0 when its samples are a run of consecutive ``.fam`` columns (the kernel's fast path)."""
-
-    def __init__(self, lib, path, chr_name, populations, start, end, anc_allele_file, n_threads):
-        samples = [name for names, _ in populations for name in names]
-        ploidies = [int(ploidy) for names, ploidy in populations for _ in names]
-        self.idx = _Index(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads)
-        self.pops, lo = [], 0
-        for names, ploidy in populations:
-            cols = np.ascontiguousarray(self.idx.col_of_slot[lo : lo + len(names)])
-            run = len(cols) > 0 and np.array_equal(cols, np.arange(cols[0], cols[0] + len(cols), dtype=np.int32))
-            self.pops.append({"lo": lo, "n_ind": len(names), "ploidy": int(ploidy), "cols": cols, "first_col": int(cols[0]) if run else -1})
-            lo += len(names)
-
-    def raise_flagged(self, status, unfit) -> None:
-        """``status`` / ``unfit`` = per population the int32 array over the rows of the index, or None when nothing is
-        flagged there.  A refused row (a heterozygous call at ploidy 1, an index out of range) is reported first, in
-        the words of the int8 route: the first such row, and in it the lowest slot of the request.  Then the first row
-        that does not fit two bits."""
-        idx = self.idx
-        for flags, report in ((status, self._refused), (unfit, self._unfit)):
-            rows = [int(np.flatnonzero(f)[0]) if f is not None and f.any() else idx.n_rows for f in flags]
-            k = min(rows, default=idx.n_rows)
-            if k < idx.n_rows:
-                p = rows.index(k)  # populations in request order: the first one flagged holds the lowest slot
-                report(k, self.pops[p], int(flags[p][k]))
-
-    def _refused(self, k: int, pop: dict, st: int) -> None:
-        one = np.zeros(1, dtype=np.int32)
-        one[0] = st if st == _ffi_plink.SAI_PLINK_STATUS_BAD_INDEX else self.idx.n_slots - (pop["lo"] + pop["n_ind"] - st)
-        self.idx.raise_flagged(one, k)
-
-    def _unfit(self, k: int, pop: dict, uf: int) -> None:
-        idx = self.idx
-        sample = idx.samples[pop["lo"] + pop["n_ind"] - uf]
-        raise ValueError(
-            f"{idx.prefix}.bed: missing call of sample {sample} at variant {_variant_id(idx.prefix, int(idx.file_row[k]))} "
-            f"(position {int(idx.pos[k])}) in a row flipped by the ancestral allele: its dosage is 4, which the 2-bit layout "
-            "cannot hold; read this fileset with --layout int8"
-        )
+_WHOLE_ROW = (_ffi_plink.SAI_PLINK_STATUS_BAD_INDEX,)  # the status codes that stand for a row, not for one of its slots
 
 
-def _packed_bytes(n_sites: int, n_ind: int) -> int:
-    """``sai_packed2_bytes`` (saihip.h), restated for the host reader: the sanitizer build has no kernel unit."""
-    return -(-n_sites // 64) * ((n_ind // 64) * 256 + ((n_ind % 64 + 15) // 16) * 64) * 4
+def _packed_plan(lib, path, chr_name, populations, start, end, anc_allele_file, n_threads) -> _PackedPlan:
+    return _PackedPlan(lambda samples, ploidies: _Index(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads),
+                       populations, _WHOLE_ROW, ".bed", _variant_id)  # fmt: skip
 
 
 def load_packed(path, chr_name: str, populations, start: Optional[int] = None, end: Optional[int] = None,
@@ -334,34 +255,26 @@ def load_packed(path, chr_name: str, populations, start: Optional[int] = None, e
     lib = _ffi_packed_ingest.load_host()
     _ffi_plink.load_host()
     n_threads = n_threads or default_threads()
-    plan = _PackedPlan(lib, path, chr_name, populations, start, end, anc_allele_file, n_threads)
+    plan = _packed_plan(lib, path, chr_name, populations, start, end, anc_allele_file, n_threads)
     idx = plan.idx
     blocks = [np.zeros(_packed_bytes(idx.n_rows, pop["n_ind"]), dtype=np.uint8) for pop in plan.pops]
     if idx.n_slots == 0 or idx.n_rows == 0:
         return idx.pos, blocks, idx.n_matched, idx.n_anc
-    cap = int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
     status = [np.zeros(idx.n_rows, dtype=np.int32) for _ in plan.pops]
     unfit = [np.zeros(idx.n_rows, dtype=np.int32) for _ in plan.pops]
-    buf = None
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    fd = os.open(idx.prefix + ".bed", os.O_RDONLY)
-    try:
-        for k0, k1, rib, n_batch_rows, reads in idx.batches(cap):
-            nbytes = n_batch_rows * idx.row_bytes
-            if buf is None or buf.size < nbytes:
-                buf = np.empty(nbytes, dtype=np.uint8)
-            pread_into(fd, memoryview(buf), reads, idx.prefix + ".bed")
-            if k1 == k0:
-                continue
-            for p, pop in enumerate(plan.pops):
-                if pop["n_ind"]:
-                    check_io(lib, lib.sai_bed_pack2_host(
-                        ptr(buf), n_batch_rows, idx.row_bytes, k1 - k0, ptr(rib), ptr(idx.flip[k0:k1]), idx.n_fam, pop["n_ind"],
-                        ptr(pop["cols"]), pop["first_col"], pop["ploidy"], ptr(blocks[p]), idx.n_rows, k0, ptr(status[p][k0:k1]),
-                        ptr(unfit[p][k0:k1]), n_threads,
-                    ))  # fmt: skip
-    finally:
-        os.close(fd)
+
+    def decode(buf, batch):
+        k0, k1, rib, n_batch_rows, _ = batch
+        for p, pop in enumerate(plan.pops):
+            if k1 > k0 and pop["n_ind"]:
+                check_io(lib, lib.sai_bed_pack2_host(
+                    ptr(buf), n_batch_rows, idx.row_bytes, k1 - k0, ptr(rib), ptr(idx.flip[k0:k1]), idx.n_fam, pop["n_ind"],
+                    ptr(pop["cols"]), pop["first_col"], pop["ploidy"], ptr(blocks[p]), idx.n_rows, k0, ptr(status[p][k0:k1]),
+                    ptr(unfit[p][k0:k1]), n_threads,
+                ))  # fmt: skip
+
+    read_batches(idx.prefix + ".bed", idx.staged(_cap(buffer_bytes)), decode)
     plan.raise_flagged(status, unfit)
     return idx.pos, blocks, idx.n_matched, idx.n_anc
 
@@ -370,96 +283,48 @@ def load_packed_device(eng, path, chr_name: str, populations, start: Optional[in
                        anc_allele_file: Optional[str] = None, n_threads: Optional[int] = None, buffer_bytes: Optional[int] = None,
                        trace: Optional[dict] = None):  # fmt: skip
     """(pos int32 host array [n], [PackedPop per population], n_matched, n_anc_entries): the rows of the region
-    decoded straight into one packed2 block per population, left in HBM.  The index, the batches, the two pinned
-    buffers, their device twins and the side stream are those of ``load_dosage_device``; behind each copy one
-    ``sai_bed_pack2`` call per population writes the batch's sites of that population's block.  No int8
-    [record][slot] tensor exists on this route.  ``trace`` as in ``load_dosage_device``."""
+    decoded straight into one packed2 block per population, left in HBM.  The index, the batches, the staging and
+    the side stream are those of ``load_dosage_device``; behind each copy one ``sai_bed_pack2`` call per population
+    writes the batch's sites of that population's block.  No int8 [record][slot] tensor exists on this route.
+    ``trace`` as in ``load_dosage_device``."""
     import time
 
     import torch
-
-    from ..engine import PackedPop
 
     _ffi_plink.load()
     _ffi_packed_ingest.load()
     lib = eng.lib
     t0 = time.perf_counter()
-    plan = _PackedPlan(lib, path, chr_name, populations, start, end, anc_allele_file, n_threads)
+    plan = _packed_plan(lib, path, chr_name, populations, start, end, anc_allele_file, n_threads)
     idx = plan.idx
     if trace is not None:
         trace["index"] = trace.get("index", 0.0) + time.perf_counter() - t0
         trace["bed_bytes"] = 0
-    packed = []
-    for pop in plan.pops:
-        nbytes = int(lib.sai_packed2_bytes(idx.n_rows, pop["n_ind"]))
-        if nbytes < 0:
-            raise ValueError("packed2: population too large")
-        packed.append(PackedPop(torch.empty((nbytes,), dtype=torch.uint8, device=eng.device), idx.n_rows, pop["n_ind"]))
+    packed = plan.device_blocks(eng)
     if idx.n_slots == 0 or idx.n_rows == 0:
         return idx.pos, packed, idx.n_matched, idx.n_anc
-    cap = int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
-    batches = idx.batches(cap)
-    first = next(batches)  # a buffer smaller than one row is refused before anything is page-locked
-    st = staging(eng, "_plink_state", cap, lambda: {"pinned": pair(cap), "rows": pair(cap, device=eng.device),
-                                                    "stream": torch.cuda.Stream(device=eng.device)})  # fmt: skip
-    pinned, dev_rows, side = st["pinned"], st["rows"], st["stream"]
+    cap = _cap(buffer_bytes)
     # per population: status and unfit of every row, side by side in one tensor
     flags = torch.empty((len(plan.pops), 2, idx.n_rows), dtype=torch.int32, device=eng.device)
     cols_dev = [None if pop["first_col"] >= 0 else torch.from_numpy(pop["cols"]).to(eng.device) for pop in plan.pops]
-    copied = [None, None]  # per buffer: the event behind its last H2D copy
-    keep = []
-    fd = os.open(idx.prefix + ".bed", os.O_RDONLY)
-    try:
-        side.wait_stream(torch.cuda.current_stream(eng.device))  # the blocks and `flags` were allocated on the current stream
-        b = 0
 
-        def all_batches():
-            yield first
-            yield from batches
+    def launch(rows_ptr, batch, side):
+        k0, k1, rib, n_batch_rows, _ = batch
+        if k1 == k0:
+            return None
+        d_rib = torch.from_numpy(rib).to(eng.device, non_blocking=True)
+        d_flip = torch.from_numpy(idx.flip[k0:k1]).to(eng.device, non_blocking=True)
+        for p, pop in enumerate(plan.pops):
+            if pop["n_ind"]:
+                _ffi.check(
+                    lib.sai_bed_pack2(eng.ctx, C.c_void_p(rows_ptr), n_batch_rows, idx.row_bytes, k1 - k0, eng._ptr(d_rib), eng._ptr(d_flip),
+                                      idx.n_fam, pop["n_ind"], eng._ptr(cols_dev[p]), pop["first_col"], pop["ploidy"],
+                                      C.c_void_p(packed[p].data.data_ptr()), idx.n_rows, k0, C.c_void_p(flags[p, 0].data_ptr() + 4 * k0),
+                                      C.c_void_p(flags[p, 1].data_ptr() + 4 * k0), C.c_void_p(side.cuda_stream))
+                )  # fmt: skip
+        return d_rib, d_flip
 
-        for k0, k1, rib, n_batch_rows, reads in all_batches():
-            nbytes = n_batch_rows * idx.row_bytes
-            if copied[b] is not None:
-                copied[b].synchronize()  # the copy two batches back has left this pinned buffer
-            t1 = time.perf_counter()
-            pread_into(fd, memoryview(pinned[b].numpy()), reads, idx.prefix + ".bed")
-            if trace is not None:
-                trace["file_read"] = trace.get("file_read", 0.0) + time.perf_counter() - t1
-                trace["bed_bytes"] += nbytes
-            serial = trace is not None and trace.get("serial")
-            with torch.cuda.stream(side):
-                t1 = time.perf_counter()
-                dev_rows[b][:nbytes].copy_(pinned[b][:nbytes], non_blocking=True)
-                copied[b] = torch.cuda.Event()
-                copied[b].record(side)
-                if serial:
-                    side.synchronize()
-                    trace["h2d"] = trace.get("h2d", 0.0) + time.perf_counter() - t1
-                    t1 = time.perf_counter()
-                if k1 > k0:
-                    d_rib = torch.from_numpy(rib).to(eng.device, non_blocking=True)
-                    d_flip = torch.from_numpy(idx.flip[k0:k1]).to(eng.device, non_blocking=True)
-                    keep.append((d_rib, d_flip))
-                    for p, pop in enumerate(plan.pops):
-                        if pop["n_ind"]:
-                            _ffi.check(
-                                lib.sai_bed_pack2(eng.ctx, C.c_void_p(dev_rows[b].data_ptr()), n_batch_rows, idx.row_bytes, k1 - k0,
-                                                  eng._ptr(d_rib), eng._ptr(d_flip), idx.n_fam, pop["n_ind"], eng._ptr(cols_dev[p]),
-                                                  pop["first_col"], pop["ploidy"], C.c_void_p(packed[p].data.data_ptr()), idx.n_rows, k0,
-                                                  C.c_void_p(flags[p, 0].data_ptr() + 4 * k0), C.c_void_p(flags[p, 1].data_ptr() + 4 * k0),
-                                                  C.c_void_p(side.cuda_stream))
-                            )  # fmt: skip
-                if serial:
-                    side.synchronize()
-                    trace["decode"] = trace.get("decode", 0.0) + time.perf_counter() - t1
-            b ^= 1
-    finally:
-        os.close(fd)
-        side.synchronize()  # also on an error: the staging buffers are reused by the next call
-    live = [p for p, pop in enumerate(plan.pops) if pop["n_ind"]]
-    if live and bool(flags[live].any()):
-        host = flags.cpu().numpy()
-        plan.raise_flagged([host[p, 0] if p in live else None for p in range(len(plan.pops))],
-                           [host[p, 1] if p in live else None for p in range(len(plan.pops))])  # fmt: skip
+    side = staged_copy(eng, "_plink_state", cap, idx.prefix + ".bed", idx.staged(cap), launch, trace, "bed_bytes")
+    plan.raise_flagged_device(flags)
     torch.cuda.current_stream(eng.device).wait_stream(side)
     return idx.pos, packed, idx.n_matched, idx.n_anc
