@@ -240,7 +240,7 @@ extern "C" int sai_eigenstrat_decode(sai_ctx* ctx, int32_t encoding, const uint8
   SAI_HIP(hipMemsetAsync(status, 0, static_cast<size_t>(n_out_rows) * sizeof(int32_t), st));
   // a memory-bound pass: enough workgroups to fill the chip, grid-stride beyond that
   const int64_t want = (a.n_chunks + kGenoBlock - 1) / kGenoBlock;
-  const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;
+  const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;  // past this cap: tests/test_grid_stride_device.py
   const dim3 grid(static_cast<unsigned>(want < cap ? want : cap));
   if (text) hipLaunchKernelGGL(geno_decode_kernel<TextFetch>, grid, dim3(kGenoBlock), 0, st, a);
   else hipLaunchKernelGGL(geno_decode_kernel<PackedFetch>, grid, dim3(kGenoBlock), 0, st, a);

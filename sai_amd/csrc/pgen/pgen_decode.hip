@@ -193,7 +193,7 @@ extern "C" int sai_pgen_decode(sai_ctx* ctx, const uint8_t* bytes, int64_t n_byt
   hipStream_t st = static_cast<hipStream_t>(stream);
   SAI_HIP(hipMemsetAsync(status, 0, static_cast<size_t>(n_out_rows) * sizeof(int32_t), st));
   // a wavefront per row; beyond the 16 per CU that are resident at once rows are taken in a grid stride
-  const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;
+  const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;  // past this cap: tests/test_grid_stride_device.py
   hipLaunchKernelGGL(pgen_decode_kernel, dim3(static_cast<unsigned>(n_out_rows < cap ? n_out_rows : cap)), dim3(kWave), 0, st, a);
   return check_launch("pgen_decode");
 }

@@ -207,7 +207,7 @@ extern "C" int sai_pgen_pack2(sai_ctx* ctx, const uint8_t* bytes, int64_t n_byte
   packed2_set_groups(a, n_ind);
   // a wavefront per row (and per padding site); beyond the 16 per CU that are resident at once rows are taken in a grid stride
   const int64_t want = n_out_rows + a.n_pad;
-  const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;
+  const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;  // past this cap: tests/test_grid_stride_device.py
   const dim3 grid(static_cast<unsigned>(want < cap ? want : cap)), block(kWave);
   SAI_PACKED2_LAUNCH(pgen_pack2_kernel, a, ploidy, n_out_rows, grid, block, stream);
   return check_launch("pgen_pack2");

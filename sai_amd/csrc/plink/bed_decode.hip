@@ -196,7 +196,7 @@ extern "C" int sai_plink_decode(sai_ctx* ctx, const uint8_t* rows, int64_t n_bat
   SAI_HIP(hipMemsetAsync(status, 0, static_cast<size_t>(n_out_rows) * sizeof(int32_t), st));
   // a memory-bound pass: enough workgroups to fill the chip, grid-stride beyond that
   const int64_t want = (a.n_chunks + kDecodeBlock - 1) / kDecodeBlock;
-  const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;
+  const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;  // past this cap: tests/test_grid_stride_device.py
   hipLaunchKernelGGL(bed_decode_kernel, dim3(static_cast<unsigned>(want < cap ? want : cap)), dim3(kDecodeBlock), 0, st, a);
   return check_launch("bed_decode");
 }

@@ -199,7 +199,7 @@ extern "C" int sai_bed_pack2(sai_ctx* ctx, const uint8_t* rows, int64_t n_batch_
   a.n_units = n_tiles * a.runs_per_tile;
   // a memory-bound pass: enough workgroups to fill the chip, grid-stride beyond that
   const int64_t want = (a.n_units + kPackBlock / 64 - 1) / (kPackBlock / 64);
-  const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;
+  const int64_t cap = static_cast<int64_t>(ctx->n_cu) * 16;  // past this cap: tests/test_grid_stride_device.py
   const dim3 grid(static_cast<unsigned>(want < cap ? want : cap)), block(kPackBlock);
   SAI_PACKED2_LAUNCH(bed_pack2_kernel, a, ploidy, n_out_rows, grid, block, stream);
   return check_launch("bed_pack2");

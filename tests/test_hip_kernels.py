@@ -389,6 +389,23 @@ def test_fused_site_pass_equals_two_kernels(eng):
         eng.site_pass(pops, pl, sets * 2)
 
 
+def oracle_decisions(mats, pl, specs):
+    """Per parameter set (w, x, y_list, anc) of ``specs``: (condition, site inverted, target frequency with the
+    inversion applied), bool / bool / f64 per site, by the numpy oracle.  ``mats`` = ref, tgt, sources."""
+    from oracle import sai_oracle as O
+
+    n_sites = len(mats[0])
+    m64 = [m.astype(np.int64) for m in mats]
+    plain = [O.allele_freq(g, int(p)) for g, p in zip(m64, pl)]
+    ok = np.all([np.isfinite(f) & (f >= 0) & (f <= 1) for f in plain], axis=0)
+    out = []
+    for w, x, y, anc in specs:
+        _, tfo, cond = O.matching_loci(m64[0], m64[1], m64[2:], w, y, pl, anc)
+        mirror = np.all([O._COMPARE[op](f, 1 - yy) for f, (op, yy) in zip(plain[2:], y)], axis=0)
+        out.append((cond, np.zeros(n_sites, bool) if anc else (mirror & ok), tfo))
+    return out
+
+
 @pytest.mark.parametrize("n_sites", [1, 63, 64, 65, 1000])
 def test_flag_planes_are_the_oracle_decisions_bit_for_bit(eng, n_sites):
     """The documented row layout (saihip.h): bit b of a word = site 64 t + b; word 0 "any" (all ones from
@@ -396,7 +413,6 @@ def test_flag_planes_are_the_oracle_decisions_bit_for_bit(eng, n_sites):
     call has a set without ancestral alleles) -- from the stand-alone kernel, the fused pass and the packed2
     pass alike, spare bits of the last tile 0; with ancestral alleles everywhere the inverted words do not
     exist; and flag_bytes' U candidates are the oracle's."""
-    from oracle import sai_oracle as O
     from sai_amd import _ffi
 
     rng = np.random.default_rng(n_sites)
@@ -414,14 +430,9 @@ def test_flag_planes_are_the_oracle_decisions_bit_for_bit(eng, n_sites):
     assert np.array_equal(words, fused.cpu().numpy().view(np.uint64)) and np.array_equal(words, packed.cpu().numpy().view(np.uint64))
     assert np.all(words[:, 0] == np.uint64(0xFFFFFFFFFFFFFFFF)) and np.all(words[:, 7:] == 0)  # 1 + 2 * 3 words used
     site = np.arange(n_sites)
-    m64 = [m.astype(np.int64) for m in mats]
-    plain = [O.allele_freq(g, 2) for g in m64]
-    ok = np.all([np.isfinite(f) & (f >= 0) & (f <= 1) for f in plain], axis=0)
     bytes_ = eng.flag_bytes(planes, n_sites, sets, tf).cpu().numpy()
-    for s, (w, x, y, anc) in enumerate(specs):
-        _, tfo, cond = O.matching_loci(m64[0], m64[1], m64[2:], w, y, pl, anc)
-        mirror = np.all([O._COMPARE[op](f, 1 - yy) for f, (op, yy) in zip(plain[2:], y)], axis=0)
-        want = {1 + s: cond, 1 + 3 + s: np.zeros(n_sites, bool) if anc else (mirror & ok)}
+    for s, ((w, x, y, anc), (cond, inverted, tfo)) in enumerate(zip(specs, oracle_decisions(mats, pl, specs))):
+        want = {1 + s: cond, 1 + 3 + s: inverted}
         for k, bits in want.items():
             got = (words[site // 64, k] >> (site % 64).astype(np.uint64)) & np.uint64(1)
             assert np.array_equal(got.astype(bool), bits), (s, k)

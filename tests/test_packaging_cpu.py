@@ -87,7 +87,7 @@ def test_install_builds_the_library_and_the_sai_command_prints_the_reference_fla
     # compiler and recompile every unit into site-packages because the wheel has no object directory
     rank = tmp_path / "rank.py"
     rank.write_text("import os, torch.distributed as dist\ndist.init_process_group('gloo')\n"
-                    "print('rank', dist.get_rank(), flush=True)\ndist.destroy_process_group()\n")
+                    "os.write(1, b'rank %d\\n' % dist.get_rank())\ndist.destroy_process_group()\n")  # one write: the ranks share the pipe
     code = ("import sai_amd._build as b, sai_amd.launcher as L, sys; assert b.shipped_library_is_current(); "
             f"sys.exit(L.launch_ranks(2, [], script={str(rank)!r}))")
     no_hipcc = {**env, "PATH": "/usr/bin:/bin", "HIPCC": "/nonexistent/hipcc"}
