@@ -58,7 +58,9 @@ def _run_score(args: argparse.Namespace) -> None:
 
 def add_score_parser(subparsers) -> None:
     parser = subparsers.add_parser("score", help="Run the score command based on specified parameters.")
-    parser.add_argument("--vcf", type=existed_file, default=None, help="Path to the VCF file containing variant data.")
+    parser.add_argument("--vcf", type=existed_file, default=None, help="Path to the VCF file containing variant data: plain, gzip or bgzip text, or a BGZF-compressed BCF 2.2 file "
+                        "(told by its content; a raw, uncompressed BCF is refused; records with more than two GT values per sample, "
+                        "triploid and higher, are decoded by a slower path of the GPU kernel).")
     # not a flag of the reference: the same genotypes as a PLINK 1 binary fileset, decoded on the GPU
     parser.add_argument("--bfile", type=existed_fileset, default=None, metavar="PREFIX",
                         help="Prefix of a PLINK 1 binary fileset (PREFIX.bed + PREFIX.bim + PREFIX.fam, variant-major) to "

@@ -1,0 +1,299 @@
+"""BCF 2.x files (BGZF-compressed, as ``bcftools view -Ob`` writes them) as an input of ``score``.
+
+A BCF record holds its genotypes as a dense typed integer array, normally one byte per allele.  The host
+(``sai_bcf_stream_*``, sai_amd/csrc/bcf/bcf_index.cpp) inflates the members with several threads, walks the record
+chain, selects the rows as the VCF reader does and copies the GT array of every selected row -- nothing else of
+the record -- into two staging buffers in turn; ``sai_bcf_decode`` (bcf/bcf_decode.hip) recodes the arrays into the
+int8 [record][sample] block ``sai_tokenize_gt`` writes for the same calls as VCF text, so everything behind the
+reader is shared with the VCF route.  The host inflate bounds the route, as it does for a gzip VCF (profiles/bcf_ingest.txt).  The format
+rules as they are implemented, what of them has not been checked against ``bcftools``, and what is refused are in
+DESIGN_INGEST.md ("BCF files").
+
+The surface is that of the fileset readers: ``fileset_prefix`` (the path itself when it is a BCF: detection is by
+content), ``scan_first_last``, ``load_dosage`` / ``load_dosage_device`` (what ``native_vcf.load_dosage`` /
+``device_vcf.load_dosage_device`` return) and ``release_buffers``.  Every request of a (sample, ploidy) is a slot.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+
+from .. import _ffi, _ffi_bcf
+from ._ingest import check_io, default_threads, pair, region_args, staging
+
+BUFFER_BYTES = 32 << 20  # as the other routes; SAI_AMD_INGEST_BUFFER overrides it
+
+_probed: dict = {}  # (path, size, mtime) -> is a BCF
+_scanned: dict = {}  # (path, size, mtime, chromosome) -> (first, last, n_records_total, n_samples)
+
+
+def _file_key(path):
+    text = os.fspath(path)
+    st = os.stat(text)
+    return (os.path.abspath(text), st.st_size, st.st_mtime_ns)
+
+
+def fileset_prefix(path) -> Optional[str]:
+    """The path itself when it names a BGZF file whose inflated stream starts as a BCF (``sai_bcf_probe``), else
+    None.  The name does not matter; the answer is remembered per (path, size, mtime)."""
+    if path is None:
+        return None
+    text = os.fspath(path)
+    try:
+        if not os.path.isfile(text):
+            return None
+        key = _file_key(text)
+        if key not in _probed:
+            with open(text, "rb") as f:
+                gz = f.read(2) == b"\x1f\x8b"  # only a gzip member is worth inflating
+            _probed[key] = bool(gz and _ffi_bcf.load_host().sai_bcf_probe(os.fsencode(text)))
+        return text if _probed[key] else None
+    except OSError:
+        return None
+
+
+def is_fileset(path) -> bool:
+    return fileset_prefix(path) is not None
+
+
+def _scan(path, chr_name: str):
+    key = (*_file_key(path), str(chr_name))
+    if key not in _scanned:
+        lib = _ffi_bcf.load_host()
+        v = [C.c_int64(-1) for _ in range(4)]
+        check_io(lib, lib.sai_bcf_scan(os.fsencode(path), str(chr_name).encode(), *[C.byref(x) for x in v]))
+        _scanned[key] = tuple(int(x.value) for x in v)
+    return _scanned[key]
+
+
+def scan_first_last(path, chr_name: str):
+    """First and last position of the first contiguous run of ``chr_name`` (None, None if absent):
+    ``native_vcf.scan_first_last`` for a BCF.  One walk of the whole file, remembered per (path, size, mtime,
+    chromosome) for the life of the process."""
+    first, last, _, _ = _scan(path, chr_name)
+    return (None, None) if first < 0 else (first, last)
+
+
+def header_counts(path) -> tuple:
+    """(records of the file, samples of its header): what stays resident is their product.  A BCF has no record
+    count in its header, so this is a walk of the whole file -- ``sai_bcf_scan`` counts while it looks for a
+    chromosome, and any chromosome's remembered scan answers; where there is none yet, the scan is asked for the
+    empty name, which no contig has: it selects nothing and counts everything (and is remembered like the others)."""
+    for key, got in _scanned.items():
+        if key[:3] == _file_key(path):
+            return got[2], got[3]
+    _, _, n_records, n_samples = _scan(path, "")
+    return n_records, n_samples
+
+
+def _cap(buffer_bytes) -> int:
+    return int(buffer_bytes or os.environ.get("SAI_AMD_INGEST_BUFFER", BUFFER_BYTES))
+
+
+class _Stream:
+    """One ``sai_bcf_stream``: the batches of a region and, once the first has come, the selection."""
+
+    def __init__(self, lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffers, cap):
+        self.lib, self.path, self.chr_name = lib, os.fspath(path), str(chr_name)
+        self.samples = list(samples)
+        self.ploidies = np.asarray([int(p) for p in ploidies], dtype=np.int32)
+        self.handle = C.c_void_p()
+        args = region_args(path, chr_name, start, end, samples, ploidies, anc_allele_file, n_threads)
+        check_io(lib, lib.sai_bcf_stream_open(*args, C.c_void_p(buffers[0]), C.c_void_p(buffers[1]), cap, C.byref(self.handle)))
+        self.cols = None  # int32 [n slots]: the sample column of every slot
+        self.n_cols = 0
+        self.first_col = self.uniform_ploidy = -1
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.lib.sai_bcf_stream_close(self.handle)
+        self.handle = None
+
+    def next(self):
+        """(buffer, bytes, pos, flip, off, width, L) of the next batch -- copies of the tables -- or None at the end."""
+        buf, n_bytes, n_rows, done = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32()
+        ptrs = [C.c_void_p() for _ in range(5)]
+        check_io(self.lib, self.lib.sai_bcf_stream_next(self.handle, C.byref(buf), C.byref(n_bytes), C.byref(n_rows),
+                                                        *[C.byref(p) for p in ptrs], C.byref(done)))  # fmt: skip
+        if done.value:
+            return None
+        n = int(n_rows.value)
+        kinds = ((C.c_int32, np.int32), (C.c_uint8, np.uint8), (C.c_int64, np.int64), (C.c_uint8, np.uint8), (C.c_int32, np.int32))
+        tables = [np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+                  for p, (ct, dt) in zip(ptrs, kinds)]  # fmt: skip
+        if self.cols is None:
+            self._select()
+        return (int(buf.value), int(n_bytes.value), *tables)
+
+    def _select(self) -> None:
+        n = len(self.samples)
+        cols, n_file = np.empty(max(n, 1), dtype=np.int32), C.c_int32()
+        check_io(self.lib, self.lib.sai_bcf_stream_selection(self.handle, cols.ctypes.data_as(C.c_void_p), n, C.byref(n_file), None, None))
+        self.cols, self.n_cols = cols[:n].copy(), int(n_file.value)
+        # the two promises that select the kernel's fast path
+        self.first_col = int(cols[0]) if n and np.array_equal(self.cols, np.arange(cols[0], cols[0] + n, dtype=np.int32)) else -1
+        self.uniform_ploidy = int(self.ploidies[0]) if n and bool((self.ploidies == self.ploidies[0]).all()) else 0
+
+    def stats(self) -> dict:
+        """The producer's seconds by phase and its byte counts (``sai_bcf_stream_stats``), once the stream is read to its end."""
+        t = [C.c_double() for _ in range(5)]
+        n = [C.c_int64() for _ in range(2)]
+        check_io(self.lib, self.lib.sai_bcf_stream_stats(self.handle, *[C.byref(x) for x in t], *[C.byref(x) for x in n]))
+        names = ("file_read", "inflate", "walk", "copy_to_staging", "wait_for_buffer")
+        return {**{k: float(x.value) for k, x in zip(names, t)}, "inflated_bytes": int(n[0].value), "staged_bytes": int(n[1].value)}
+
+    def counts(self) -> tuple:
+        """(rows matched before polarisation, entries of the ancestral-allele table) of the finished walk."""
+        n_matched, n_anc = C.c_int64(), C.c_int64()
+        if self.lib.sai_bcf_stream_selection(self.handle, None, 0, None, C.byref(n_matched), C.byref(n_anc)):
+            return 0, 0
+        return int(n_matched.value), int(n_anc.value)
+
+    def raise_flagged(self, buf, n_bytes, pos, flip, off, width, length, status) -> None:
+        """The first flagged row of a batch as the reader's ValueError, naming the record and the sample."""
+        bad = np.flatnonzero(status)
+        if bad.size == 0:
+            return
+        r, st = int(bad[0]), int(status[bad[0]])
+        where, name = f"{self.chr_name}:{int(pos[r])}", None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        one, one_status = np.zeros(1, dtype=np.int8), np.zeros(1, dtype=np.int32)
+        for s in range(len(self.samples)):  # the error path: slot by slot until one says it
+            check_io(self.lib, self.lib.sai_bcf_decode_host(ptr(buf), n_bytes, 1, ptr(off[r : r + 1]), ptr(width[r : r + 1]), ptr(length[r : r + 1]),
+                                                            ptr(flip[r : r + 1]), self.n_cols, 1, ptr(self.cols[s : s + 1]),
+                                                            ptr(self.ploidies[s : s + 1]), ptr(one), ptr(one_status), 1))  # fmt: skip
+            if int(one_status[0]) == st:
+                name = self.samples[s]
+                break
+        if st == _ffi_bcf.SAI_BCF_STATUS_RANGE:
+            raise ValueError(f"{self.path}: dosage outside the int8 range at {where} (sample {name})")
+        if st == _ffi_bcf.SAI_BCF_STATUS_BAD_VALUE:
+            raise ValueError(f"{self.path}: record {where}: the GT vector of sample {name} holds a reserved value: the record is damaged")
+        raise ValueError(f"{self.path}: record {where} was decoded with an index outside its range")
+
+
+def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[int], start: Optional[int] = None,
+                end: Optional[int] = None, anc_allele_file: Optional[str] = None, n_threads: Optional[int] = None,
+                buffer_bytes: Optional[int] = None):  # fmt: skip
+    """(pos int32 [n], dosage int8 [n][len(samples)], n_matched, n_anc_entries) for one region, decoded on the
+    host (``sai_bcf_decode_host``): the ``SAI_AMD_INGEST=host`` route and the yardstick of the kernel."""
+    lib = _ffi_bcf.load_host()
+    n_threads = n_threads or default_threads()
+    cap, n = _cap(buffer_bytes), len(samples)
+    bufs = [np.empty(cap, dtype=np.uint8) for _ in range(2)]
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    pos_parts, dos_parts = [], []
+    with _Stream(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, [b.ctypes.data for b in bufs], cap) as stream:
+        while True:
+            got = stream.next()
+            if got is None:
+                break
+            b, n_bytes, pos, flip, off, width, length = got
+            pos_parts.append(pos)
+            dos = np.empty((len(pos), n), dtype=np.int8)
+            if n and len(pos):
+                status = np.empty(len(pos), dtype=np.int32)
+                check_io(lib, lib.sai_bcf_decode_host(ptr(bufs[b]), n_bytes, len(pos), ptr(off), ptr(width), ptr(length), ptr(flip), stream.n_cols, n,
+                                                      ptr(stream.cols), ptr(stream.ploidies), ptr(dos), ptr(status), n_threads))  # fmt: skip
+                stream.raise_flagged(bufs[b], n_bytes, pos, flip, off, width, length, status)
+            dos_parts.append(dos)
+        n_matched, n_anc = stream.counts()
+    pos = np.concatenate(pos_parts) if pos_parts else np.zeros(0, dtype=np.int32)
+    dos = np.concatenate(dos_parts) if dos_parts else np.zeros((0, n), dtype=np.int8)
+    return pos, dos, n_matched, n_anc
+
+
+def release_buffers(eng) -> None:
+    """Drop the staging ``load_dosage_device`` keeps between calls."""
+    st = eng.__dict__.pop("_bcf_state", None)
+    if st:
+        st["stream"].synchronize()
+        st.clear()
+
+
+def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidies: Sequence[int],
+                       start: Optional[int] = None, end: Optional[int] = None, anc_allele_file: Optional[str] = None,
+                       n_threads: Optional[int] = None, buffer_bytes: Optional[int] = None, trace: Optional[dict] = None):  # fmt: skip
+    """(pos int32 host array [n], dosage int8 DEVICE tensor [n][len(samples)], n_matched, n_anc_entries):
+    ``load_dosage`` with the result left in HBM.  The loop of ``device_vcf.load_dosage_device``: the producer thread
+    fills one pinned buffer while the other one is copied on a side stream and decoded behind the copy; the producer
+    may refill a buffer once its copy has left it.  A row the kernel flags is handed to the host route, which raises
+    the error that names the record and the sample.  ``trace`` (a dict) collects the producer's seconds per phase
+    (``_Stream.stats``: file_read, inflate, walk, copy_to_staging, wait_for_buffer, and the bytes inflated and staged);
+    with ``trace["serial"]`` set the side stream is synchronised behind every copy and every kernel, so ``h2d`` and
+    ``decode`` are timed on their own, by the host clock (and nothing overlaps)."""
+    import time
+
+    import torch
+
+    _ffi_bcf.load()
+    lib = eng.lib
+    cap, n = _cap(buffer_bytes), len(samples)
+    st = staging(eng, "_bcf_state", cap, lambda: {"pinned": pair(cap), "rows": pair(cap, device=eng.device),
+                                                  "stream": torch.cuda.Stream(device=eng.device)})  # fmt: skip
+    pinned, dev_rows, side = st["pinned"], st["rows"], st["stream"]
+    current = torch.cuda.current_stream(eng.device)
+    side.wait_stream(current)  # the outputs are allocated on the current stream: what used their memory before is done first
+    pos_parts, outs, stats, tables = [], [], [], [None, None]
+    cols_dev = ploidy_dev = None  # only where the promises of the fast path do not hold
+    try:
+        with _Stream(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, [t.data_ptr() for t in pinned], cap) as stream:
+            copied = None
+            while True:
+                if copied is not None:
+                    copied.synchronize()  # the H2D copy of the previous batch has left its pinned buffer
+                got = stream.next()
+                if got is None:
+                    break
+                b, n_bytes, pos, flip, off, width, length = got
+                pos_parts.append(pos)
+                if n == 0 or len(pos) == 0:
+                    continue
+                out = torch.empty((len(pos), n), dtype=torch.int8, device=eng.device)
+                status = torch.empty((len(pos),), dtype=torch.int32, device=eng.device)
+                serial = trace is not None and trace.get("serial")
+                with torch.cuda.stream(side):
+                    t1 = time.perf_counter()
+                    dev_rows[b][:n_bytes].copy_(pinned[b][:n_bytes], non_blocking=True)
+                    copied = torch.cuda.Event()
+                    copied.record(side)
+                    if serial:
+                        side.synchronize()
+                        trace["h2d"] = trace.get("h2d", 0.0) + time.perf_counter() - t1
+                        t1 = time.perf_counter()
+                    if cols_dev is None and stream.first_col < 0:
+                        cols_dev = torch.from_numpy(stream.cols).to(eng.device)
+                    if ploidy_dev is None and stream.uniform_ploidy <= 0:
+                        ploidy_dev = torch.from_numpy(stream.ploidies).to(eng.device)
+                    d_off, d_width, d_len, d_flip = (torch.from_numpy(a).to(eng.device, non_blocking=True) for a in (off, width, length, flip))
+                    tables[b] = (d_off, d_width, d_len, d_flip)  # those of two batches back go: allocated and used on this stream alone
+                    _ffi.check(
+                        lib.sai_bcf_decode(eng.ctx, C.c_void_p(dev_rows[b].data_ptr()), n_bytes, len(pos), eng._ptr(d_off), eng._ptr(d_width),
+                                           eng._ptr(d_len), eng._ptr(d_flip), stream.n_cols, n,
+                                           eng._ptr(cols_dev), stream.first_col, eng._ptr(ploidy_dev), max(stream.uniform_ploidy, 0),
+                                           C.c_void_p(out.data_ptr()), 0, eng._ptr(status), C.c_void_p(side.cuda_stream))
+                    )  # fmt: skip
+                    if serial:
+                        side.synchronize()
+                        trace["decode"] = trace.get("decode", 0.0) + time.perf_counter() - t1
+                outs.append(out)
+                stats.append(status)
+            n_matched, n_anc = stream.counts()
+            if trace is not None:
+                trace.update(stream.stats())
+    finally:
+        side.synchronize()  # also on an error: the staging buffers are reused by the next call
+    if stats and bool(torch.cat(stats).any()):
+        load_dosage(path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes)
+        raise ValueError(f"{os.fspath(path)}: the GPU decoder flagged a row the host reader accepts")
+    current.wait_stream(side)
+    pos = np.concatenate(pos_parts) if pos_parts else np.zeros(0, dtype=np.int32)
+    if not outs:
+        return pos, torch.empty((len(pos), n), dtype=torch.int8, device=eng.device), n_matched, n_anc
+    return pos, torch.cat(outs) if len(outs) > 1 else outs[0], n_matched, n_anc

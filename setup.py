@@ -24,7 +24,7 @@ def build_library() -> None:
         _build.build()
         dst = ROOT / "sai_amd" / "include"
         dst.mkdir(exist_ok=True)
-        for header in ("saihip.h", "saihip_plink.h", "saihip_eigenstrat.h", "saihip_pgen.h", "saihip_packed_ingest.h", "saihip_pgen_packed.h"):
+        for header in ("saihip.h", "saihip_plink.h", "saihip_eigenstrat.h", "saihip_pgen.h", "saihip_packed_ingest.h", "saihip_pgen_packed.h", "saihip_bcf.h"):
             shutil.copy2(ROOT / "include" / header, dst / header)  # travel as package data
     finally:
         sys.path.remove(str(ROOT))
@@ -45,7 +45,8 @@ class DevelopWithLibrary(develop):
 # on top of the table in pyproject.toml: the sources of the fileset readers live in directories of their own
 EXTRA_PACKAGE_DATA = {"sai_amd": ["csrc/plink/*.hip", "csrc/plink/*.hpp", "csrc/plink/*.cpp",
                                   "csrc/eigenstrat/*.hip", "csrc/eigenstrat/*.hpp", "csrc/eigenstrat/*.cpp",
-                                  "csrc/pgen/*.hip", "csrc/pgen/*.hpp", "csrc/pgen/*.cpp"]}
+                                  "csrc/pgen/*.hip", "csrc/pgen/*.hpp", "csrc/pgen/*.cpp",
+                                  "csrc/bcf/*.hip", "csrc/bcf/*.cpp"]}
 
 
 class WithExtraPackageData(setuptools.Distribution):
