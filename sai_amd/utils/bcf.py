@@ -1,13 +1,23 @@
 """BCF 2.x files (BGZF-compressed, as ``bcftools view -Ob`` writes them) as an input of ``score``.
 
-A BCF record holds its genotypes as a dense typed integer array, normally one byte per allele.  The host
-(``sai_bcf_stream_*``, sai_amd/csrc/bcf/bcf_index.cpp) inflates the members with several threads, walks the record
-chain, selects the rows as the VCF reader does and copies the GT array of every selected row -- nothing else of
-the record -- into two staging buffers in turn; ``sai_bcf_decode`` (bcf/bcf_decode.hip) recodes the arrays into the
-int8 [record][sample] block ``sai_tokenize_gt`` writes for the same calls as VCF text, so everything behind the
-reader is shared with the VCF route.  The host inflate bounds the route, as it does for a gzip VCF (profiles/bcf_ingest.txt).  The format
-rules as they are implemented, what of them has not been checked against ``bcftools``, and what is refused are in
-DESIGN_INGEST.md ("BCF files").
+A BCF record holds its genotypes as a dense typed integer array, normally one byte per allele.  ``sai_bcf_decode``
+(bcf/bcf_decode.hip) recodes the arrays of the selected rows into the int8 [record][sample] block ``sai_tokenize_gt``
+writes for the same calls as VCF text, so everything behind the reader is shared with the VCF route.  Two routes
+bring the arrays to it:
+
+* the GPU route (``_load_device_walk``; the default of ``load_dosage_device`` unless ``SAI_AMD_GPU_INFLATE=0``): the
+  compressed members cross PCIe as they are (``sai_bcf_feed_*``), ``sai_inflate_bgzf``
+  inflates them, ``sai_bcf_chain_segments`` / ``sai_bcf_stitch`` / ``sai_bcf_record_heads`` (bcf/bcf_walk.hip,
+  bcf/bcf_feed.cpp) find the records, 64 bytes per record come back for the row selection, and the GT arrays are
+  decoded where the inflater left them.  Anything unusual -- a member the inflater refuses, a chain the stitch cannot
+  follow, a selected row with an error flag, a row the decoder flags -- throws the partial result away and runs
+* the host route from the start (``sai_bcf_stream_*``, bcf/bcf_index.cpp): the host inflates the members with several
+  threads, walks the record chain, selects the rows and copies the GT array of every selected row -- nothing else of
+  the record -- into two staging buffers in turn.  It words every error about the file (profiles/bcf_ingest.txt,
+  profiles/bcf_gpu_walk.txt).
+
+The format rules as they are implemented, what of them has not been checked against ``bcftools``, and what is refused
+are in DESIGN_INGEST.md ("BCF files" and "BCF files: members inflated and records found on the GPU").
 
 The surface is that of the fileset readers: ``fileset_prefix`` (the path itself when it is a BCF: detection is by
 content), ``scan_first_last``, ``load_dosage`` / ``load_dosage_device`` (what ``native_vcf.load_dosage`` /
@@ -22,10 +32,13 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .. import _ffi, _ffi_bcf
+from .. import _ffi, _ffi_bcf, _ffi_bcf_device
 from ._ingest import check_io, default_threads, pair, region_args, staging
 
 BUFFER_BYTES = 32 << 20  # as the other routes; SAI_AMD_INGEST_BUFFER overrides it
+
+SEG_BYTES = 16384  # SAI_AMD_BCF_SEG_BYTES overrides it for tools/bcf_rate.py (a power of two in 256 .. 65536)
+CARRY_ROOM = 64 << 20  # at most this much of a batch's tail is carried in front of the next one
 
 _probed: dict = {}  # (path, size, mtime) -> is a BCF
 _scanned: dict = {}  # (path, size, mtime, chromosome) -> (first, last, n_records_total, n_samples)
@@ -60,13 +73,39 @@ def is_fileset(path) -> bool:
     return fileset_prefix(path) is not None
 
 
+def _gpu_walk_wanted() -> bool:
+    return os.environ.get("SAI_AMD_GPU_INFLATE", "1") != "0" and os.environ.get("SAI_AMD_INGEST", "device") != "host"
+
+
+def _scan_on_device(path, chr_name: str):
+    """The scan through the GPU route -- no samples, nothing decoded, every record of the file counted -- or None
+    where there is no GPU, the knob says no or the route hands the file over: the host scan says what is wrong."""
+    if not _gpu_walk_wanted():
+        return None
+    try:
+        import torch
+
+        if not torch.cuda.is_available():
+            return None
+        from ..engine import Engine
+
+        eng = Engine.get()
+        icap = int(os.environ.get("SAI_AMD_INFLATE_BATCH", 0)) or _inflate_batch(path)
+        return _load_device_walk(eng, path, chr_name, [], [], None, None, None, icap, None, whole_file=True)[4]
+    except (ImportError, ValueError, _HostRoute):
+        return None
+
+
 def _scan(path, chr_name: str):
     key = (*_file_key(path), str(chr_name))
     if key not in _scanned:
-        lib = _ffi_bcf.load_host()
-        v = [C.c_int64(-1) for _ in range(4)]
-        check_io(lib, lib.sai_bcf_scan(os.fsencode(path), str(chr_name).encode(), *[C.byref(x) for x in v]))
-        _scanned[key] = tuple(int(x.value) for x in v)
+        got = _scan_on_device(path, chr_name)
+        if got is None:
+            lib = _ffi_bcf.load_host()
+            v = [C.c_int64(-1) for _ in range(4)]
+            check_io(lib, lib.sai_bcf_scan(os.fsencode(path), str(chr_name).encode(), *[C.byref(x) for x in v]))
+            got = tuple(int(x.value) for x in v)
+        _scanned[key] = got
     return _scanned[key]
 
 
@@ -211,17 +250,211 @@ def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[
 
 def release_buffers(eng) -> None:
     """Drop the staging ``load_dosage_device`` keeps between calls."""
-    st = eng.__dict__.pop("_bcf_state", None)
-    if st:
-        st["stream"].synchronize()
-        st.clear()
+    for key in ("_bcf_state", "_bcf_walk_state"):
+        st = eng.__dict__.pop(key, None)
+        if st:
+            st["stream"].synchronize()
+            st.clear()
+
+
+class _HostRoute(Exception):
+    """The GPU route does not serve this read: the host route takes it from the start."""
+
+
+def _inflate_batch(path) -> int:
+    from .device_vcf import _inflate_batch_for
+
+    return _inflate_batch_for(path)
 
 
 def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidies: Sequence[int],
                        start: Optional[int] = None, end: Optional[int] = None, anc_allele_file: Optional[str] = None,
                        n_threads: Optional[int] = None, buffer_bytes: Optional[int] = None, trace: Optional[dict] = None):  # fmt: skip
     """(pos int32 host array [n], dosage int8 DEVICE tensor [n][len(samples)], n_matched, n_anc_entries):
-    ``load_dosage`` with the result left in HBM.  The loop of ``device_vcf.load_dosage_device``: the producer thread
+    ``load_dosage`` with the result left in HBM.  The GPU route (``_load_device_walk``) unless ``SAI_AMD_GPU_INFLATE=0``,
+    in batches of ``SAI_AMD_INFLATE_BATCH`` inflated bytes (default: by the file's size,
+    as for a bgzip VCF); where that route hands the read over, and otherwise, the host route (``_load_host_inflate``).
+    ``trace`` (a dict) gets ``route`` = ``"device"`` / ``"host"`` and the route's seconds per phase."""
+    if _gpu_walk_wanted():
+        icap = int(os.environ.get("SAI_AMD_INFLATE_BATCH", 0)) or _inflate_batch(path)
+        try:
+            got = _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, icap, trace)
+            if trace is not None:
+                trace["route"] = "device"
+            return got[:4]
+        except _HostRoute:
+            pass
+    if trace is not None:
+        trace["route"] = "host"
+    return _load_host_inflate(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes, trace)
+
+
+def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, icap, trace, whole_file=False):
+    """(pos, dosage, n_matched, n_anc, (first, last, records seen, samples of the file)) through the GPU route, or
+    ``_HostRoute``.  Per batch, on a side stream: the compressed members and their table go to the device; ``sai_inflate_bgzf`` writes their
+    text behind the carry of the batch before; ``sai_bcf_chain_segments`` summarises every segment and the summaries
+    come back for ``sai_bcf_stitch``; ``sai_bcf_record_heads`` writes a head per record and the heads come back for
+    ``sai_bcf_feed_select``; the row tables go up and ``sai_bcf_decode`` reads the GT arrays out of the text.  The
+    bytes from the first incomplete record on are copied, device to device, to the front of the other text buffer.
+    The feed's thread reads batch k + 1 from the file meanwhile.  With ``trace["serial"]`` the stream is synchronised
+    behind every step, so ``h2d``, ``inflate_gpu``, ``walk_gpu`` and ``decode`` are timed on their own."""
+    import time
+
+    import torch
+
+    _ffi_bcf.load()
+    lib = _ffi_bcf_device.load()
+    n, text_path = len(samples), os.fspath(path)
+    seg_bytes, max_heads = int(os.environ.get("SAI_AMD_BCF_SEG_BYTES", SEG_BYTES)), _ffi_bcf_device.SAI_BCF_MAX_HEADS
+    room = min(icap, CARRY_ROOM)
+    text_cap = room + max(icap, 65536)
+    comp_cap = max(icap // 2, 1 << 17) + 65540  # a batch is closed early when its members fill this first
+    st = staging(eng, "_bcf_walk_state", icap, lambda: {"pinned": pair(comp_cap), "comp": pair(comp_cap, device=eng.device),
+                                                        "text": pair(text_cap + 16, device=eng.device),
+                                                        "stream": torch.cuda.Stream(device=eng.device)})  # fmt: skip
+    pinned, comp_dev, text_dev, side = st["pinned"], st["comp"], st["text"], st["stream"]
+    current = torch.cuda.current_stream(eng.device)
+    side.wait_stream(current)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    names = (C.c_char_p * n)(*[s.encode() for s in samples])
+    feed = C.c_void_p()
+    rc = lib.sai_bcf_feed_open(os.fsencode(text_path), str(chr_name).encode(), -1 if start is None else int(start), -1 if end is None else int(end),
+                               n, names, os.fsencode(anc_allele_file) if anc_allele_file else None, C.c_void_p(pinned[0].data_ptr()),
+                               C.c_void_p(pinned[1].data_ptr()), comp_cap, icap, int(whole_file), C.byref(feed))  # fmt: skip
+    if rc:
+        raise _HostRoute("open")
+    serial = trace is not None and trace.get("serial")
+    laps = {}
+
+    def lap(name, t1):
+        if serial:
+            side.synchronize()
+            laps[name] = laps.get(name, 0.0) + time.perf_counter() - t1
+        return time.perf_counter()
+
+    pos_parts, outs, stats = [], [], []
+    try:
+        n_contigs, n_file, gt_key = C.c_int32(), C.c_int32(), C.c_int64()
+        lib.sai_bcf_feed_selection(feed, None, 0, None, 0, C.byref(n_contigs), C.byref(n_file), C.byref(gt_key), *[None] * 5)
+        contigs, cols = np.zeros(max(n_contigs.value, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.int32)
+        check_io(lib, lib.sai_bcf_feed_selection(feed, ptr(cols), n, ptr(contigs), n_contigs.value, *[None] * 8))
+        cols, n_cols = cols[:n].copy(), int(n_file.value)
+        pl = np.asarray([int(p) for p in ploidies], dtype=np.int32)
+        first_col = int(cols[0]) if n and np.array_equal(cols, np.arange(cols[0], cols[0] + n, dtype=np.int32)) else -1
+        uniform = int(pl[0]) if n and bool((pl == pl[0]).all()) and 1 <= int(pl[0]) <= 64 else 0
+        if n and (int(pl.min()) < 1 or int(pl.max()) > 64):
+            raise _HostRoute("ploidy")  # the host route words it
+        with torch.cuda.stream(side):
+            d_contigs = torch.from_numpy(contigs).to(eng.device)
+            d_cols = torch.from_numpy(cols).to(eng.device) if n and first_col < 0 else None
+            d_pl = torch.from_numpy(pl).to(eng.device) if n and uniform == 0 else None
+        carry, done = 0, False
+        while not done:
+            b, n_comp, n_members, n_text, e0, end_of_file = C.c_int32(), C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32()
+            members = C.c_void_p()
+            if lib.sai_bcf_feed_next(feed, C.byref(b), C.byref(n_comp), C.byref(n_members), C.byref(members), C.byref(n_text), C.byref(e0),
+                                     C.byref(end_of_file)):  # fmt: skip
+                raise _HostRoute("reader")
+            if end_of_file.value:
+                break
+            b, n_comp, nm, n_text = int(b.value), int(n_comp.value), int(n_members.value), int(n_text.value)
+            n_bytes = carry + n_text  # at most text_cap: carry <= room, and a batch is icap bytes or one member
+            entry = 0 if carry else int(e0.value)
+            table = np.ctypeslib.as_array(C.cast(members, C.POINTER(C.c_uint8)), shape=(nm * 32,)).copy()
+            n_seg = -(-n_bytes // seg_bytes)
+            text = text_dev[b]
+            with torch.cuda.stream(side):
+                t1 = time.perf_counter()
+                comp_dev[b][:n_comp].copy_(pinned[b][:n_comp], non_blocking=True)
+                d_table = torch.from_numpy(table).to(eng.device, non_blocking=True)
+                t1 = lap("h2d", t1)
+                d_member_status = torch.empty((nm,), dtype=torch.int32, device=eng.device)
+                _ffi.check(lib.sai_inflate_bgzf(eng.ctx, C.c_void_p(comp_dev[b].data_ptr()), n_comp, C.c_void_p(d_table.data_ptr()), nm,
+                                                C.c_void_p(text.data_ptr() + carry), n_text, C.c_void_p(d_member_status.data_ptr()),
+                                                C.c_void_p(side.cuda_stream)))  # fmt: skip
+                t1 = lap("inflate_gpu", t1)
+                d_chains = torch.empty((n_seg * max_heads * 16,), dtype=torch.uint8, device=eng.device)
+                d_info = torch.empty((n_seg,), dtype=torch.int32, device=eng.device)
+                _ffi.check(lib.sai_bcf_chain_segments(eng.ctx, C.c_void_p(text.data_ptr()), n_bytes, seg_bytes, max_heads, C.c_void_p(d_contigs.data_ptr()),
+                                                      int(n_contigs.value), n_cols, C.c_void_p(d_chains.data_ptr()), C.c_void_p(d_info.data_ptr()),
+                                                      C.c_void_p(side.cuda_stream)))  # fmt: skip
+                bad_members = int(d_member_status.count_nonzero())  # waits for the stream
+                chains, info = d_chains.cpu().numpy(), d_info.cpu().numpy()
+                lib.sai_bcf_feed_release(feed)  # the compressed bytes and the table have left their buffer
+                if bad_members:
+                    raise _HostRoute("member")
+                seg_entry, seg_first = np.empty(n_seg, dtype=np.int64), np.empty(n_seg, dtype=np.int64)
+                n_records, carry_from, verdict = C.c_int64(), C.c_int64(), C.c_int32()
+                check_io(lib, lib.sai_bcf_stitch(ptr(chains), ptr(info), n_bytes, seg_bytes, max_heads, entry, ptr(seg_entry), ptr(seg_first),
+                                                 C.byref(n_records), C.byref(carry_from), C.byref(verdict)))  # fmt: skip
+                if verdict.value:
+                    raise _HostRoute("stitch")
+                n_records, carry_from = int(n_records.value), int(carry_from.value)
+                heads = np.zeros(0, dtype=_ffi_bcf_device.HEAD)
+                if n_records:
+                    d_entry, d_first = torch.from_numpy(seg_entry).to(eng.device, non_blocking=True), torch.from_numpy(seg_first).to(eng.device, non_blocking=True)
+                    d_heads = torch.empty((n_records * 64,), dtype=torch.uint8, device=eng.device)
+                    _ffi.check(lib.sai_bcf_record_heads(eng.ctx, C.c_void_p(text.data_ptr()), n_bytes, seg_bytes, C.c_void_p(d_entry.data_ptr()),
+                                                        C.c_void_p(d_first.data_ptr()), carry_from, n_records, int(gt_key.value), int(n > 0),
+                                                        C.c_void_p(d_heads.data_ptr()), C.c_void_p(side.cuda_stream)))  # fmt: skip
+                    heads = d_heads.cpu().numpy().view(_ffi_bcf_device.HEAD)
+                t1 = lap("walk_gpu", t1)
+            n_rows, sel_done, verdict = C.c_int64(), C.c_int32(), C.c_int32()
+            tabs = [C.c_void_p() for _ in range(5)]
+            check_io(lib, lib.sai_bcf_feed_select(feed, ptr(heads), n_records, C.byref(n_rows), *[C.byref(t) for t in tabs], C.byref(sel_done),
+                                                  C.byref(verdict)))  # fmt: skip
+            if verdict.value:
+                raise _HostRoute("select")
+            done, nr = bool(sel_done.value), int(n_rows.value)
+            kinds = ((C.c_int32, np.int32), (C.c_uint8, np.uint8), (C.c_int64, np.int64), (C.c_uint8, np.uint8), (C.c_int32, np.int32))
+            pos, flip, off, width, length = (np.ctypeslib.as_array(C.cast(t, C.POINTER(ct)), shape=(nr,)).astype(dt, copy=True) if nr
+                                             else np.zeros(0, dtype=dt) for t, (ct, dt) in zip(tabs, kinds))  # fmt: skip
+            pos_parts.append(pos)
+            if n and nr:
+                out = torch.empty((nr, n), dtype=torch.int8, device=eng.device)
+                status = torch.empty((nr,), dtype=torch.int32, device=eng.device)
+                side.wait_stream(current)
+                with torch.cuda.stream(side):
+                    t1 = time.perf_counter()
+                    d_off, d_width, d_len, d_flip = (torch.from_numpy(a).to(eng.device, non_blocking=True) for a in (off, width, length, flip))
+                    _ffi.check(lib.sai_bcf_decode(eng.ctx, C.c_void_p(text.data_ptr()), n_bytes, nr, eng._ptr(d_off), eng._ptr(d_width), eng._ptr(d_len),
+                                                  eng._ptr(d_flip), n_cols, n, eng._ptr(d_cols), first_col, eng._ptr(d_pl), uniform,
+                                                  C.c_void_p(out.data_ptr()), 0, eng._ptr(status), C.c_void_p(side.cuda_stream)))  # fmt: skip
+                    t1 = lap("decode", t1)
+                outs.append(out)
+                stats.append(status)
+            carry = n_bytes - carry_from
+            if done:  # the selection has stopped: what lies behind the region is not looked at, as on the host
+                break
+            if carry > room:
+                raise ValueError(f"{text_path}: a record does not fit a batch of {icap} inflated bytes: raise SAI_AMD_INFLATE_BATCH")
+            if carry:
+                with torch.cuda.stream(side):
+                    text_dev[b ^ 1][:carry].copy_(text[carry_from:n_bytes], non_blocking=True)
+        if not done and carry:
+            raise _HostRoute("trailing bytes")  # the stream ends inside a record: the host route words it
+        v = [C.c_int64() for _ in range(5)]
+        check_io(lib, lib.sai_bcf_feed_selection(feed, None, 0, None, 0, None, None, None, *[C.byref(x) for x in v]))
+        n_matched, n_anc, n_seen, first, last = (int(x.value) for x in v)
+        if trace is not None:
+            t = [C.c_double() for _ in range(4)]
+            comp_bytes = C.c_int64()
+            lib.sai_bcf_feed_stats(feed, *[C.byref(x) for x in t], C.byref(comp_bytes))
+            trace.update({k: float(x.value) for k, x in zip(("file_read", "header_inflate", "select", "wait_for_buffer"), t)})
+            trace.update(laps, comp_bytes=int(comp_bytes.value))
+    finally:
+        lib.sai_bcf_feed_close(feed)
+        side.synchronize()  # also on an error: the staging buffers are reused by the next call
+    if stats and bool(torch.cat(stats).any()):
+        raise _HostRoute("a flagged row")
+    current.wait_stream(side)
+    pos = np.concatenate(pos_parts) if pos_parts else np.zeros(0, dtype=np.int32)
+    dos = torch.cat(outs) if len(outs) > 1 else outs[0] if outs else torch.empty((len(pos), n), dtype=torch.int8, device=eng.device)
+    return pos, dos, n_matched, n_anc, (first, last, n_seen, n_cols)
+
+
+def _load_host_inflate(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes, trace):
+    """The host route of ``load_dosage_device``.  The loop of ``device_vcf.load_dosage_device``: the producer thread
     fills one pinned buffer while the other one is copied on a side stream and decoded behind the copy; the producer
     may refill a buffer once its copy has left it.  A row the kernel flags is handed to the host route, which raises
     the error that names the record and the sample.  ``trace`` (a dict) collects the producer's seconds per phase

@@ -6,13 +6,16 @@ timed): as bgzip VCF text and as BCF, the latter with the tests' writer (tests/b
 ``encode_record`` and its ``bgzf_members`` at zlib level 6; the GT payload of a record comes from numpy).  Then, in
 ONE call,
 
-  * reads chromosome 1 through ``bcf.load_dosage_device``, through ``device_vcf.load_dosage_device`` with the host
-    inflating (``SAI_AMD_GPU_INFLATE=0``) and through the same with the GPU inflating -- each --repeats times after
-    one warm-up, with the files in the page cache, overlapped as `score` reads them (host clock around a device
-    synchronise) -- reports the median, and checks that the three dosage blocks are equal;
-  * reads the BCF once more with every phase on its own: the producer's file read, inflate, walk and copy into
-    staging (``sai_bcf_stream_stats``), and H2D and kernel with the side stream synchronised behind each;
-  * says which phase bounds the route.
+  * reads chromosome 1 through ``bcf.load_dosage_device`` on its host route (``SAI_AMD_GPU_INFLATE=0``), through
+    ``device_vcf.load_dosage_device`` with the host inflating (``SAI_AMD_GPU_INFLATE=0``) and through the same with the
+    GPU inflating, and through ``bcf.load_dosage_device`` on its GPU route (``bcf_gpu_walk``: members inflated and
+    records found on the GPU) -- each --repeats times after one warm-up, with the files in the page cache, overlapped
+    as `score` reads them (host clock around a device synchronise) -- reports the median, and checks that the four
+    dosage blocks are equal;
+  * reads the BCF once more on its host route with every phase on its own: the producer's file read, inflate, walk
+    and copy into staging (``sai_bcf_stream_stats``), and H2D and kernel with the side stream synchronised behind each;
+  * reads it on the GPU route with every phase on its own, once per segment size of --seg-bytes;
+  * says which phase bounds the host route.
 
 ``--trace-summary DIR --staged-bytes N`` reads the CSVs a ``rocprofv3 --kernel-trace --memory-copy-trace --stats
 --output-format csv -d DIR -- python tools/bcf_rate.py ...`` run left behind (N: that run's "staged" line) and prints
@@ -136,7 +139,8 @@ def main() -> int:
     ap.add_argument("--samples", type=int, default=2002)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--seed", type=int, default=20262)
-    ap.add_argument("--routes", default="bcf,vcf_host_inflate,vcf_gpu_inflate", help="comma-separated; the default is all three")
+    ap.add_argument("--routes", default="bcf,vcf_host_inflate,vcf_gpu_inflate,bcf_gpu_walk", help="comma-separated; the default is all four")
+    ap.add_argument("--seg-bytes", default="4096,16384,65536", help="segment sizes of the GPU route's serial readings, comma-separated")
     ap.add_argument("--dir", default=None, help="where the inputs are written (kept and reused when given; default: a temporary directory)")
     ap.add_argument("--trace-summary", default=None, metavar="DIR")
     ap.add_argument("--staged-bytes", type=int, default=0, help="with --trace-summary: the GT bytes the BCF route of the profiled run staged")
@@ -165,7 +169,15 @@ def main() -> int:
     ploidies, genotypes = [2] * len(names), args.rows * args.samples
 
     def read_bcf(trace=None):
+        os.environ["SAI_AMD_GPU_INFLATE"] = "0"
         return bcf.load_dosage_device(eng, bcf_path, "1", names, ploidies, trace=trace)
+
+    def read_bcf_gpu_walk(trace=None):
+        os.environ["SAI_AMD_GPU_INFLATE"] = "1"
+        trace = {} if trace is None else trace
+        got = bcf.load_dosage_device(eng, bcf_path, "1", names, ploidies, trace=trace)
+        assert trace["route"] == "device", "the GPU route handed the read to the host route"
+        return got
 
     def read_vcf(gpu_inflate):
         def read(trace=None):
@@ -174,7 +186,14 @@ def main() -> int:
 
         return read
 
-    routes = {"bcf": read_bcf, "vcf_host_inflate": read_vcf(False), "vcf_gpu_inflate": read_vcf(True)}
+    def timed_read(read):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        read()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t
+
+    routes = {"bcf": read_bcf, "vcf_host_inflate": read_vcf(False), "vcf_gpu_inflate": read_vcf(True), "bcf_gpu_walk": read_bcf_gpu_walk}
     before = os.environ.get("SAI_AMD_GPU_INFLATE")
     result = {"rows": args.rows, "samples": args.samples, "routes": {}}
     reference = None
@@ -201,10 +220,6 @@ def main() -> int:
         print(f"  median {1e3 * median:.1f} ms (spread {1e3 * spread:.1f}) = {genotypes / median / 1e9:.3f} G genotypes/s")
         result["routes"][route] = {"ms": [round(1e3 * t, 2) for t in whole], "median_ms": round(1e3 * median, 2), "spread_ms": round(1e3 * spread, 2),
                                    "genotypes_per_s": round(genotypes / median)}  # fmt: skip
-    if before is None:
-        os.environ.pop("SAI_AMD_GPU_INFLATE", None)
-    else:
-        os.environ["SAI_AMD_GPU_INFLATE"] = before
     del reference
     if "bcf" in result["routes"]:
         base = result["routes"]["bcf"]["median_ms"]
@@ -212,6 +227,7 @@ def main() -> int:
             if route != "bcf":
                 print(f"bcf against {route}: {got['median_ms'] / base:.2f} times the genotypes per second")
         trace = {"serial": True}
+        os.environ["SAI_AMD_GPU_INFLATE"] = "0"
         torch.cuda.synchronize()
         t = time.perf_counter()
         read_bcf(trace)
@@ -230,6 +246,36 @@ def main() -> int:
         result["bcf_phases_ms"] = {k: round(1e3 * trace.get(k, 0.0), 2) for k in phases}
         result["bcf_bounded_by"] = slowest
         bcf.release_buffers(eng)
+    if "bcf_gpu_walk" in result["routes"]:
+        if "bcf" in result["routes"]:
+            print(f"bcf_gpu_walk against bcf: {result['routes']['bcf']['median_ms'] / result['routes']['bcf_gpu_walk']['median_ms']:.2f} times the genotypes per second")
+        phases = ("file_read", "header_inflate", "wait_for_buffer", "h2d", "inflate_gpu", "walk_gpu", "select", "decode")
+        seg_before = os.environ.get("SAI_AMD_BCF_SEG_BYTES")
+        result["bcf_gpu_walk_phases_ms"] = {}
+        for seg in args.seg_bytes.split(","):
+            os.environ["SAI_AMD_BCF_SEG_BYTES"] = seg
+            read_bcf_gpu_walk()  # warm-up at this segment size
+            trace = {"serial": True}
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            read_bcf_gpu_walk(trace)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t
+            whole = sorted(timed_read(read_bcf_gpu_walk) for _ in range(3))
+            print(f"bcf_gpu_walk, seg_bytes {seg}: every phase on its own ({1e3 * dt:.1f} ms in all; {trace['comp_bytes']} compressed bytes over PCIe; "
+                  f"walk_gpu = both kernels, the summaries and heads copied back and the stitch), overlapped median of 3: {1e3 * whole[1]:.1f} ms; ms per phase:")  # fmt: skip
+            for name in phases:
+                print(f"  {name:16s} {1e3 * trace.get(name, 0.0):9.1f}")
+            result["bcf_gpu_walk_phases_ms"][seg] = {**{k: round(1e3 * trace.get(k, 0.0), 2) for k in phases}, "overlapped_median_ms": round(1e3 * whole[1], 2)}
+        if seg_before is None:
+            os.environ.pop("SAI_AMD_BCF_SEG_BYTES", None)
+        else:
+            os.environ["SAI_AMD_BCF_SEG_BYTES"] = seg_before
+        bcf.release_buffers(eng)
+    if before is None:
+        os.environ.pop("SAI_AMD_GPU_INFLATE", None)
+    else:
+        os.environ["SAI_AMD_GPU_INFLATE"] = before
     print(json.dumps(result))
     if holder is not None:
         holder.cleanup()
