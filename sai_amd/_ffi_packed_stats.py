@@ -1,0 +1,58 @@
+"""ctypes binding of the packed-statistics entry points of libsaihip.so (include/saihip_packed_stats.h): per-site allele
+frequencies straight from packed2 blocks, the site half of fd / df / Danc / Dplus in the 2-bit layout.
+
+They live in the same shared library as the entry points of ``_ffi`` (and their host part in the sanitizer
+build of the host units), but in a header and a table of their own, with their own version number:
+``load()`` / ``load_host()`` take the handle ``_ffi`` returns and declare the prototypes below on it.  A
+library without them is an error, as everywhere in this package.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _ffi
+
+SAI_PACKED_STATS_ABI_VERSION = 1
+SAI_PACKED_FREQ_POPS = 9  # ref, tgt, SAI_FUSED_SRC sources, outgroup
+
+_p, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
+
+# name -> (restype, argtypes): the names include/saihip_packed_stats.h declares
+SIGNATURES = {
+    "sai_packed_stats_abi_version": (C.c_int, []),
+    "sai_packed2_site_freqs": (C.c_int, [_p, _i64, _i32, C.POINTER(_ffi.SaiPop), _p, _p]),
+    "sai_packed2_site_freqs_host": (C.c_int, [_i64, _i32, C.POINTER(_ffi.SaiPop), _p, _i32]),
+}
+
+# entry points that never touch the GPU (packed_stats/packed2_freqs_host.cpp)
+HOST_SYMBOLS = tuple(n for n in SIGNATURES if n != "sai_packed2_site_freqs")
+
+
+def _attach(lib: C.CDLL, names) -> C.CDLL:
+    if getattr(lib, "_sai_packed_stats_attached", None) == tuple(names):
+        return lib
+    for name in names:
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise RuntimeError(f"{name} is missing from libsaihip: the library was built without sai_amd/csrc/packed_stats/packed2_freqs* "
+                               "(rebuild it: `python -c 'import __graft_entry__ as g; g.build()'`)") from None  # fmt: skip
+        fn.restype, fn.argtypes = SIGNATURES[name]
+    if lib.sai_packed_stats_abi_version() != SAI_PACKED_STATS_ABI_VERSION:
+        raise RuntimeError(f"libsaihip: packed-stats ABI {lib.sai_packed_stats_abi_version()} != expected {SAI_PACKED_STATS_ABI_VERSION}")
+    lib._sai_packed_stats_attached = tuple(names)
+    return lib
+
+
+def load() -> C.CDLL:
+    """``_ffi.load()`` with every prototype of saihip_packed_stats.h declared."""
+    return _attach(_ffi.load(), tuple(SIGNATURES))
+
+
+def load_host() -> C.CDLL:
+    """``_ffi.load_host()`` with the host-only prototypes declared (the sanitizer build has no kernel)."""
+    lib = _ffi.load_host()
+    if lib is _ffi._lib:
+        return load()
+    return _attach(lib, HOST_SYMBOLS)

@@ -96,5 +96,6 @@ def add_score_parser(subparsers) -> None:
     parser.add_argument("--layout", choices=("int8", "packed2"), default=None,
                         help="Genotype layout in GPU memory: int8 (one byte per call, every input and statistic) or packed2 "
                         "(two bits per call, decoded straight from a PLINK 1 fileset given with --bfile or a PLINK 2 fileset given "
-                        "with --pfile; U and Q only, one worker). Default: $SAI_AMD_LAYOUT, else int8.")  # fmt: skip
+                        "with --pfile; U, Q, fd, df, Danc and Dplus, not DD; one worker; with --anc-alleles a missing call in a row "
+                        "flipped by the ancestral allele does not fit two bits and asks for int8). Default: $SAI_AMD_LAYOUT, else int8.")  # fmt: skip
     parser.set_defaults(runner=_run_score, score_parser=parser)

@@ -29,7 +29,7 @@ class ChunkPreprocessor(DataPreprocessor):
         num_src: int = 1,
         layout: str = "int8",
     ):
-        self.layout = layout  # "packed2": a PLINK 1 or PLINK 2 fileset decoded straight into the 2-bit layout, U and Q only
+        self.layout = layout  # "packed2": a PLINK 1 or PLINK 2 fileset decoded straight into the 2-bit layout (every statistic but DD)
         self.vcf_file = vcf_file
         self.ref_ind_file = ref_ind_file
         self.tgt_ind_file = tgt_ind_file

@@ -478,18 +478,24 @@ class FeaturePreprocessor(DataPreprocessor):
 
     def _score_packed(self, wg, combos, names, batch, sink) -> WindowBatch:
         """``score_windows`` over populations that were decoded straight into the 2-bit layout (``PackedPop``, the
-        generator was built with ``layout="packed2"``): U and Q only, every combination by one
+        generator was built with ``layout="packed2"``).  U and Q: every combination by one
         ``ResidentScorer(layout="packed2")`` that streams the blocks as they are (``packed_scorer``) -- the fused
-        packed2 site pass and the windows stage, the records of the int8 path bit for bit.  The int8 branches (shared counts, parts, DD, the ABBA-BABA family) have no packed
-        form and are not touched."""
+        packed2 site pass and the windows stage, the records of the int8 path bit for bit.  fd, df, Danc and Dplus:
+        every source of the combination (and the outgroup) through ``packed_fourpop_windows`` -- the frequencies
+        straight from the blocks, then the window kernel the int8 path runs, its doubles bit for bit; a
+        configuration with these alone builds no scorer.  The two passes each read ref, tgt and the sources once.
+        The other int8 branches (shared counts, parts, DD) have no packed form and are not touched."""
         from .. import _ffi
         from ..engine import Engine
         from ..packed_scorer import packed_scorer
+        from ..packed_stats import packed_fourpop_windows
         from ..resident import ResidentBlock
         from ..stats.stat_utils import _check_ploidy, validate_thresholds
 
-        other = [n for n in names if n not in _HIP_STATS]
-        if other:
+        uq_names = [n for n in names if n in _HIP_STATS]
+        four_names = [n for n in names if n in _FOURPOP]
+        other = [n for n in names if n not in _HIP_STATS and n not in _FOURPOP]
+        if other:  # DD; the sentence is older than the ABBA-BABA family in this layout and is kept as it was
             raise ValueError(f"the packed2 layout serves U and Q only, but {other[0]} is configured")
         eng = Engine.get()
         pc = wg.ploidy_config
@@ -503,11 +509,11 @@ class FeaturePreprocessor(DataPreprocessor):
             src_ploidies = pc.get_ploidy("src")
             ploidy = [pc.get_ploidy("ref", ref_pop), pc.get_ploidy("tgt", tgt_pop)] + list(src_ploidies)
             n_eff = min(len(src_comb), len(src_ploidies))
-            if n_eff > _ffi.SAI_FUSED_SRC:
+            if uq_names and n_eff > _ffi.SAI_FUSED_SRC:
                 raise ValueError(f"the packed2 layout streams at most {_ffi.SAI_FUSED_SRC} source populations in one pass")
             # U and Q that share w, the source conditions and the polarity mode are ONE parameter set, as on the int8 path
             sets, set_of, merged = [], [], {}
-            for name in names:
+            for name in uq_names:
                 kw = self._stat_kwargs(name, ref_pop, tgt_pop)
                 validate_thresholds(kw["w"], kw["y_list"], len(src_comb))
                 key = (float(kw["w"]), tuple((op, float(y)) for op, y in kw["y_list"]), bool(kw["anc_allele_available"]))
@@ -523,19 +529,39 @@ class FeaturePreprocessor(DataPreprocessor):
                                      kw["anc_allele_available"], n_src=n_eff) for kw, got in sets]  # fmt: skip
             for p in ploidy[: 2 + len(src_comb)]:
                 _check_ploidy(p)
-            cb = ComboBatch(ref_pop, tgt_pop, tuple(src_comb), out_pop, win, np.zeros(len(win), np.int32), list(names),
+            cb = ComboBatch(ref_pop, tgt_pop, tuple(src_comb), out_pop, win, np.zeros(len(win), np.int32), list(uq_names),
                             pos_dtype=np.dtype(pos.dtype).name)  # fmt: skip
             batch.combos.append(cb)
             if names and len(win) and pos.size:
-                keys = [("ref", ref_pop), ("tgt", tgt_pop)] + [("src", s) for s in src_comb[:n_eff]]
-                block = ResidentBlock([blocks[k] for k in keys], ploidy[: 2 + n_eff], wg.device_positions(eng, pos))
-                scorer = packed_scorer(eng, block, win, sets, cap_u=1 << 16, cap_q=1 << 16, fetch_lists=1 << 16)
+                pos_dev = wg.device_positions(eng, pos)
+                scorer = None
                 try:
-                    scorer.step()
-                    cb.uq = _rows_per_statistic(scorer.results(grow=True), set_of)
+                    if uq_names:
+                        keys = [("ref", ref_pop), ("tgt", tgt_pop)] + [("src", s) for s in src_comb[:n_eff]]
+                        block = ResidentBlock([blocks[k] for k in keys], ploidy[: 2 + n_eff], pos_dev)
+                        scorer = packed_scorer(eng, block, win, sets, cap_u=1 << 16, cap_q=1 << 16, fetch_lists=1 << 16)
+                        scorer.step()
+                        cb.uq = _rows_per_statistic(scorer.results(grow=True), set_of)
+                        lo, hi = scorer.lo, scorer.hi
+                        cb.nsnps = cb.uq.records[0]["n_sites"].astype(np.int32)
+                    else:
+                        lo, hi = eng.window_bounds(pos_dev, win[:, 0], win[:, 1])
+                        cb.nsnps = (hi - lo).cpu().numpy().astype(np.int32)
+                    if four_names:  # every source of the combination, with its own ploidy (fd_statistic.py:63-74)
+                        if len(src_ploidies) < len(src_comb):
+                            raise IndexError("list index out of range")
+                        keys = [("ref", ref_pop), ("tgt", tgt_pop)] + [("src", s) for s in src_comb]
+                        pl4 = [ploidy[0], ploidy[1]] + list(src_ploidies[: len(src_comb)])
+                        if out_pop is not None:
+                            keys.append(("outgroup", out_pop))
+                            pl4.append(pc.get_ploidy("outgroup", out_pop))
+                        for p in pl4:
+                            _check_ploidy(p)
+                        cb.four = packed_fourpop_windows(eng, [blocks[k] for k in keys], pl4, len(src_comb), out_pop is not None,
+                                                         lo, hi).cpu().numpy()  # fmt: skip
                 finally:
-                    scorer.close()
-                cb.nsnps = cb.uq.records[0]["n_sites"].astype(np.int32)
+                    if scorer is not None:
+                        scorer.close()
             if sink is not None:
                 sink(cb)
         return batch

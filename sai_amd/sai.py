@@ -91,8 +91,10 @@ def resolve_layout(layout=None) -> str:
 
 def require_packed2_input(vcf_file, config: str, num_workers: int) -> None:
     """What ``layout="packed2"`` cannot serve is refused here, before any genotype is read: the layout is decoded
-    from PLINK 1 ``.bed`` rows or PLINK 2 ``.pgen`` records on the GPU of one process and feeds the U / Q site pass.
-    (The sentence about the input predates the ``.pgen``: it is pinned word for word, and still names PLINK 1 only.)"""
+    from PLINK 1 ``.bed`` rows or PLINK 2 ``.pgen`` records on the GPU of one process and feeds the U / Q site pass
+    and the frequency pass of fd, df, Danc and Dplus (``sai_amd.packed_stats``); DD has no form in it.
+    (The sentences about the input and about the statistics predate the ``.pgen`` and the ABBA-BABA family in this
+    layout: they are pinned word for word, and still name PLINK 1 and U / Q only.)"""
     from . import launcher
     from .utils import pgen, plink
     from .utils.filesets import reader_for
@@ -104,7 +106,7 @@ def require_packed2_input(vcf_file, config: str, num_workers: int) -> None:
     if reader_for(vcf_file) not in (plink, pgen):
         raise ValueError(f"layout 'packed2' reads a PLINK 1 fileset (.bed + .bim + .fam) only, which {vcf_file} is not.")
     stats = load_config(config).statistics.root
-    other = [name for name, value in stats.items() if name not in ("U", "Q") and value is not False]
+    other = [name for name, value in stats.items() if name not in ("U", "Q", *_POLARISED) and value is not False]
     if other:
         raise ValueError(f"layout 'packed2' serves the U and Q statistics only, but {other[0]} is configured.")
 
@@ -255,9 +257,11 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
     (``WORLD_SIZE`` > 1: torchrun's environment) the call IS a rank and takes the sharded route.
 
     ``layout`` = ``"int8"`` (the default; ``SAI_AMD_LAYOUT`` overrides it) or ``"packed2"``: a PLINK 1 or PLINK 2 fileset
-    is decoded straight into the 2-bit layout and U / Q are scored on it -- four times as many sites per chunk, the same
-    files byte for byte.  What that route cannot serve is a ValueError before anything is read
-    (``require_packed2_input``); a missing call in a row flipped by the ancestral allele (dosage 4) is one while reading."""
+    is decoded straight into the 2-bit layout and U, Q, fd, df, Danc and Dplus are scored on it -- four times as many sites
+    per chunk, the same files byte for byte.  What that route cannot serve (DD among the statistics) is a ValueError
+    before anything is read (``require_packed2_input``); a missing call in a row flipped by the ancestral allele (dosage 4
+    at ploidy 2) is one while reading: with ``anc_allele_file`` -- which fd, df, Danc and Dplus require -- the layout serves
+    panels without a missing call in a flipped row, and the message names the int8 layout for the others."""
     from . import launcher
 
     num_workers = 1 if num_workers is None else int(num_workers)

@@ -25,7 +25,7 @@ def build_library() -> None:
         dst = ROOT / "sai_amd" / "include"
         dst.mkdir(exist_ok=True)
         for header in ("saihip.h", "saihip_plink.h", "saihip_eigenstrat.h", "saihip_pgen.h", "saihip_packed_ingest.h", "saihip_pgen_packed.h", "saihip_bcf.h",
-                       "saihip_bcf_device.h"):
+                       "saihip_bcf_device.h", "saihip_packed_stats.h"):
             shutil.copy2(ROOT / "include" / header, dst / header)  # travel as package data
     finally:
         sys.path.remove(str(ROOT))
@@ -47,7 +47,8 @@ class DevelopWithLibrary(develop):
 EXTRA_PACKAGE_DATA = {"sai_amd": ["csrc/plink/*.hip", "csrc/plink/*.hpp", "csrc/plink/*.cpp",
                                   "csrc/eigenstrat/*.hip", "csrc/eigenstrat/*.hpp", "csrc/eigenstrat/*.cpp",
                                   "csrc/pgen/*.hip", "csrc/pgen/*.hpp", "csrc/pgen/*.cpp",
-                                  "csrc/bcf/*.hip", "csrc/bcf/*.hpp", "csrc/bcf/*.cpp"]}
+                                  "csrc/bcf/*.hip", "csrc/bcf/*.hpp", "csrc/bcf/*.cpp",
+                                  "csrc/packed_stats/*.hip", "csrc/packed_stats/*.hpp", "csrc/packed_stats/*.cpp"]}
 
 
 class WithExtraPackageData(setuptools.Distribution):

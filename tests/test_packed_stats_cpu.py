@@ -1,0 +1,277 @@
+"""Per-site frequencies straight from packed2 blocks, on the host: ``sai_packed2_site_freqs_host`` against a numpy
+statement of include/saihip_packed_stats.h, its argument errors, the header / binding / library agreement, what
+``require_packed2_input`` admits now, and the host twin as a program of its own under the sanitizers.
+tests/test_packed_stats_device.py runs the kernel against the twin on the same shapes."""
+
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from test_bed_pack2_cpu import pack_numpy
+from test_plink_cpu import fileset_from_vcf
+
+# a tail of every width 1..4 and none; 1, 2..7, 8 and 9 full groups: single load, partial batch, full batch, batch + remainder
+N_IND = [1, 15, 16, 17, 63, 64, 65, 127, 129, 512, 513, 9 * 64 + 49]
+N_SITES = [1, 63, 64, 65, 200]
+QUIET_NAN = 0x7FF8000000000000
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    import __graft_entry__ as g
+
+    g.build()
+
+
+def ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def random_fields(rng, n_sites, n_ind, all_missing_at=None, one_called_at=None):
+    """uint8 [sites][individuals] of 2-bit fields, about a tenth of them missing; at ``all_missing_at`` nobody is called,
+    at ``one_called_at`` one individual is, at every other site at least one."""
+    fields = rng.choice(np.array([0, 1, 2, 3], dtype=np.uint8), size=(n_sites, n_ind), p=[0.5, 0.25, 0.15, 0.1])
+    fields[(fields == 3).all(axis=1), 0] = 0  # by chance nobody is called nowhere
+    if one_called_at is not None:
+        fields[one_called_at] = 3
+        fields[one_called_at, rng.integers(n_ind)] = rng.integers(0, 3)
+    if all_missing_at is not None:
+        fields[all_missing_at] = 3
+    return fields
+
+
+def freqs_numpy(fields, ploidy):
+    """saihip_packed_stats.h, field by field: (ones + 2 * twos) / ((n_ind - missing) * ploidy), NaN where nothing is called."""
+    alt = (fields == 1).sum(axis=1, dtype=np.int64) + 2 * (fields == 2).sum(axis=1, dtype=np.int64)
+    den = (fields.shape[1] - (fields == 3).sum(axis=1, dtype=np.int64)) * ploidy
+    return np.where(den > 0, alt.astype(np.float64) / np.maximum(den, 1).astype(np.float64), np.nan)
+
+
+def pops_array(blocks, n_inds, ploidies):
+    from sai_amd import _ffi
+
+    arr = (_ffi.SaiPop * len(blocks))()
+    for p, (block, n_ind, ploidy) in enumerate(zip(blocks, n_inds, ploidies)):
+        arr[p].tiles, arr[p].n_ind, arr[p].ploidy = block.ctypes.data, n_ind, ploidy
+    return arr
+
+
+def host_freqs(blocks, n_inds, ploidies, n_sites, n_threads=1):
+    """One ``sai_packed2_site_freqs_host`` call: f64 [P][n_sites]."""
+    from sai_amd import _ffi, _ffi_packed_stats
+
+    lib = _ffi_packed_stats.load_host()
+    freqs = np.full((len(blocks), n_sites), -7.0)
+    _ffi.check(lib.sai_packed2_site_freqs_host(n_sites, len(blocks), pops_array(blocks, n_inds, ploidies), ptr(freqs), n_threads), lib)
+    return freqs
+
+
+def case(rng, n_sites, n_inds):
+    """(blocks, want f64 [P][n_sites], ploidies): population 0 is entirely missing at the last site, population P - 1 has
+    one called individual at the first."""
+    ploidies = [1 + (p + n_sites) % 2 for p in range(len(n_inds))]
+    fields = [random_fields(rng, n_sites, n, all_missing_at=n_sites - 1 if p == 0 else None,
+                            one_called_at=0 if p == len(n_inds) - 1 and (p > 0 or n_sites > 1) else None)
+              for p, n in enumerate(n_inds)]  # fmt: skip
+    return [pack_numpy(f) for f in fields], np.stack([freqs_numpy(f, pl) for f, pl in zip(fields, ploidies)]), ploidies
+
+
+def same_bits(got, want):
+    return np.array_equal(np.ascontiguousarray(got).view(np.uint64), np.ascontiguousarray(want).view(np.uint64))
+
+
+@pytest.mark.parametrize("n_ind", N_IND)
+def test_host_twin_equals_the_numpy_statement(n_ind):
+    rng = np.random.default_rng(900 + n_ind)
+    for n_sites in N_SITES:
+        for ploidy in (1, 2):
+            fields = random_fields(rng, n_sites, n_ind, all_missing_at=n_sites - 1, one_called_at=0 if n_sites > 1 else None)
+            want = freqs_numpy(fields, ploidy)
+            nan_at = np.flatnonzero(np.isnan(want))
+            assert nan_at.tolist() == [n_sites - 1] and int(want.view(np.uint64)[-1]) == QUIET_NAN  # NaN there and nowhere else
+            if n_sites > 1:
+                assert want[0] in [v / ploidy for v in (0.0, 1.0, 2.0)]  # one called individual
+            for n_threads in (1, 3):
+                got = host_freqs([pack_numpy(fields)], [n_ind], [ploidy], n_sites, n_threads)
+                assert got.shape == (1, n_sites) and same_bits(got[0], want), (n_ind, n_sites, ploidy, n_threads)
+
+
+@pytest.mark.parametrize("n_pops", [1, 4, 9])
+def test_host_twin_on_several_populations_of_different_widths(n_pops):
+    rng = np.random.default_rng(40 + n_pops)
+    for n_sites in N_SITES:
+        n_inds = [N_IND[(5 * p + n_sites) % len(N_IND)] for p in range(n_pops)]
+        assert len(set(n_inds)) == n_pops
+        blocks, want, ploidies = case(rng, n_sites, n_inds)
+        assert np.isnan(want[0, -1]) and np.isnan(want).sum() == 1
+        for n_threads in (1, 3):
+            assert same_bits(host_freqs(blocks, n_inds, ploidies, n_sites, n_threads), want), (n_pops, n_sites, n_threads)
+
+
+def test_many_sites_take_several_threads():
+    """2^18 cells per thread: 5 000 sites of 129 individuals are three threads' work."""
+    rng = np.random.default_rng(3)
+    fields = random_fields(rng, 5000, 129, all_missing_at=4999, one_called_at=64)
+    assert same_bits(host_freqs([pack_numpy(fields)], [129], [2], 5000, 3)[0], freqs_numpy(fields, 2))
+
+
+def test_every_argument_error():
+    from sai_amd import _ffi, _ffi_packed_stats
+
+    lib = _ffi_packed_stats.load_host()
+    block = pack_numpy(np.zeros((2, 3), dtype=np.uint8))
+    freqs = np.full((2, 2), -7.0)
+
+    def call(n_sites=2, n_pops=2, pops="ok", out=freqs, n_ind=3, ploidy=2, null_block=False):
+        arr = pops_array([block, block], [3, n_ind], [ploidy, 2])
+        if null_block:
+            arr[1].tiles = None
+        rc = lib.sai_packed2_site_freqs_host(n_sites, n_pops, arr if pops == "ok" else None, ptr(out), 1)
+        return rc, lib.sai_last_error().decode()
+
+    assert call()[0] == 0 and (freqs == 0.0).all()
+    for kw, code, message in [
+        (dict(n_sites=-1), _ffi.SAI_ERR_ARG, "n_sites out of range"),
+        (dict(n_sites=2**31 - 1), _ffi.SAI_ERR_ARG, "n_sites out of range"),
+        (dict(n_pops=0), _ffi.SAI_ERR_ARG, "n_pops must be 1..9"),
+        (dict(n_pops=10), _ffi.SAI_ERR_ARG, "n_pops must be 1..9"),
+        (dict(pops=None), _ffi.SAI_ERR_ARG, "pops is NULL"),
+        (dict(out=None), _ffi.SAI_ERR_ARG, "NULL buffer"),
+        (dict(n_ind=0), _ffi.SAI_ERR_UNSUPPORTED, "population 1: packed2 supports 1..16777216 individuals"),
+        (dict(n_ind=2**24 + 1), _ffi.SAI_ERR_UNSUPPORTED, "population 1: packed2 supports 1..16777216 individuals"),
+        (dict(null_block=True), _ffi.SAI_ERR_ARG, "population 1: packed block is NULL"),
+        (dict(ploidy=0), _ffi.SAI_ERR_ARG, "ploidy[0] must be positive"),
+        (dict(ploidy=-2), _ffi.SAI_ERR_ARG, "ploidy[0] must be positive"),
+    ]:
+        freqs[:] = -7.0
+        rc, text = call(**kw)
+        assert rc == code and message in text, (kw, rc, text)
+        assert (freqs == -7.0).all()  # a refused call writes nothing
+    # n_sites == 0 is fine and touches nothing, whatever the populations say
+    freqs[:] = -7.0
+    assert call(n_sites=0, n_ind=0, ploidy=0, null_block=True)[0] == 0 and call(n_sites=0, out=None)[0] == 0 and (freqs == -7.0).all()
+
+
+def test_header_binding_and_library_agree_and_the_other_headers_are_untouched():
+    from sai_amd import (_build, _ffi, _ffi_bcf, _ffi_bcf_device, _ffi_eigenstrat, _ffi_packed_ingest, _ffi_packed_stats, _ffi_pgen,
+                         _ffi_pgen_packed, _ffi_plink)  # fmt: skip
+
+    strip = lambda name: re.sub(r"/\*.*?\*/", "", (ROOT / "include" / name).read_text(), flags=re.S)  # noqa: E731
+    text = strip("saihip_packed_stats.h")
+    names = sorted(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", text)))
+    assert names == sorted(_ffi_packed_stats.SIGNATURES) == ["sai_packed2_site_freqs", "sai_packed2_site_freqs_host", "sai_packed_stats_abi_version"]
+    lib = _ffi_packed_stats.load()
+    version = int(re.search(r"SAI_PACKED_STATS_ABI_VERSION (\d+)", text).group(1))
+    assert lib.sai_packed_stats_abi_version() == _ffi_packed_stats.SAI_PACKED_STATS_ABI_VERSION == version == 1
+    n_pops = int(re.search(r"SAI_PACKED_FREQ_POPS (\d+)", text).group(1))
+    assert n_pops == _ffi_packed_stats.SAI_PACKED_FREQ_POPS == 2 + _ffi.SAI_FUSED_SRC + 1 == 9
+    assert set(_ffi_packed_stats.HOST_SYMBOLS) == {"sai_packed_stats_abi_version", "sai_packed2_site_freqs_host"}
+    assert lib.sai_packed2_site_freqs(None, 1, 1, None, None, None) == _ffi.SAI_ERR_ARG and b"ctx is NULL" in lib.sai_last_error()
+    # the other headers' version numbers are as they were
+    assert lib.sai_abi_version() == _ffi.SAI_ABI_VERSION == 16
+    for module, fn, constant in [(_ffi_plink, "sai_plink_abi_version", "SAI_PLINK_ABI_VERSION"),
+                                 (_ffi_eigenstrat, "sai_eigenstrat_abi_version", "SAI_EIGENSTRAT_ABI_VERSION"),
+                                 (_ffi_pgen, "sai_pgen_abi_version", "SAI_PGEN_ABI_VERSION"),
+                                 (_ffi_packed_ingest, "sai_packed_ingest_abi_version", "SAI_PACKED_INGEST_ABI_VERSION"),
+                                 (_ffi_pgen_packed, "sai_pgen_packed_abi_version", "SAI_PGEN_PACKED_ABI_VERSION"),
+                                 (_ffi_bcf, "sai_bcf_abi_version", "SAI_BCF_ABI_VERSION"),
+                                 (_ffi_bcf_device, "sai_bcf_device_abi_version", "SAI_BCF_DEVICE_ABI_VERSION")]:  # fmt: skip
+        assert getattr(module.load(), fn)() == getattr(module, constant) == 1, fn
+    assert "packed_stats/packed2_freqs.hip" in _build.UNITS and "packed_stats/packed2_freqs_host.cpp" in _build.HOST_UNITS
+    setup = (ROOT / "setup.py").read_text()
+    assert '"saihip_packed_stats.h"' in setup and "csrc/packed_stats/*.hpp" in setup
+
+
+def test_the_abba_baba_family_is_admitted_and_dd_is_not(tmp_path, in_repo_root, monkeypatch):
+    from pgen_builder import from_bed_fileset
+
+    from sai_amd import sai as sai_mod
+
+    for name in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SAI_AMD_INGEST", "SAI_AMD_LAYOUT"):
+        monkeypatch.delenv(name, raising=False)
+    cfg = "tests/data/test.with.outgroup.config.yaml"
+    assert set(sai_mod.load_config(cfg).statistics.root) == {"fd", "df", "Danc", "Dplus"}
+    bed = str(tmp_path / "og")
+    fileset_from_vcf("tests/data/example.vcf", bed)  # admission reads no genotype: any fileset will do
+    pgen = str(tmp_path / "og_p")
+    from_bed_fileset(bed, pgen)
+    for fileset in (bed, bed + ".bed", pgen, pgen + ".pgen"):
+        assert sai_mod.require_packed2_input(fileset, cfg, 1) is None
+    dd = str(tmp_path / "with_dd.yaml")
+    with open(dd, "w") as f:
+        f.write(open(cfg).read().replace("  fd: True\n", "  fd: true\n  DD: true\n", 1))
+    assert list(sai_mod.load_config(dd).statistics.root)[:2] == ["fd", "DD"]
+    for fileset in (bed + ".bed", pgen + ".pgen"):
+        with pytest.raises(ValueError, match=r"^layout 'packed2' serves the U and Q statistics only, but DD is configured\.$"):
+            sai_mod.require_packed2_input(fileset, dd, 1)
+        with pytest.raises(ValueError, match=r"^layout 'packed2' serves the U and Q statistics only, but DD is configured\.$"):
+            sai_mod.score(vcf_file=fileset, chr_name="21", win_len=100, win_step=50, anc_allele_file="tests/data/test.with.outgroup.anc.alleles",
+                          output_file=str(tmp_path / "o" / "s.tsv"), config=dd, num_workers=1, layout="packed2")  # fmt: skip
+    # the family still asks for polarised input, in the reference's words, before anything is read or written
+    with pytest.raises(ValueError, match="The fd statistic requires polarized data"):
+        sai_mod.score(vcf_file=bed, chr_name="21", win_len=100, win_step=50, anc_allele_file=None, output_file=str(tmp_path / "o" / "s.tsv"),
+                      config=cfg, num_workers=1, layout="packed2")  # fmt: skip
+    assert not (tmp_path / "o").exists()
+
+
+def test_command_line_names_the_statistics_of_the_layout():
+    from test_plink_cpu import sai_cli
+
+    res = sai_cli("score", "--help")
+    text = " ".join(res.stdout.split())
+    assert res.returncode == 0 and "--layout {int8,packed2}" in res.stdout and "SAI_AMD_LAYOUT" in text
+    assert "a PLINK 2 fileset given with --pfile" in text and "U, Q, fd, df, Danc and Dplus, not DD" in text
+
+
+@pytest.fixture(scope="module")
+def freqs_program(tmp_path_factory):
+    """tests/native/packed_freqs_dump.cpp + packed_stats/packed2_freqs_host.cpp (and host_core.cpp, which holds the
+    error text) under ASan + UBSan, the runtimes linked in."""
+    import __graft_entry__ as entry
+
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.fail("g++ is needed to build the instrumented program")
+    out = tmp_path_factory.mktemp("packed_freqs_dump")
+    flags = [*entry.SAN_FLAGS, "-static-libasan", "-static-libubsan", f"-I{ROOT / 'include'}"]
+    sources = [entry.CSRC / "packed_stats" / "packed2_freqs_host.cpp", entry.CSRC / "host_core.cpp", ROOT / "tests" / "native" / "packed_freqs_dump.cpp"]
+    exe = out / "packed_freqs_dump"
+    res = subprocess.run([gxx, *flags, *map(str, sources), "-o", str(exe), "-lpthread", "-ldl"], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-3000:]
+    return str(exe)
+
+
+def test_host_twin_is_clean_under_asan_ubsan(tmp_path, freqs_program):
+    """The host twin run (not only compiled) under the sanitizers as a program of its own, on blocks of exactly the size
+    the header asks for: the doubles of the numpy statement and of the library."""
+    rng = np.random.default_rng(78)
+    env = dict(os.environ)
+    env.update(ASAN_OPTIONS="detect_leaks=1:exitcode=97:verify_asan_link_order=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=98")
+
+    def run(n_sites, n_threads, n_inds, ploidies, blocks):
+        args = []
+        for p, (n_ind, ploidy, block) in enumerate(zip(n_inds, ploidies, blocks)):
+            (tmp_path / f"b{p}.bin").write_bytes(block.tobytes())
+            args.append(f"{n_ind}:{ploidy}:{tmp_path / f'b{p}.bin'}")
+        return subprocess.run([freqs_program, str(n_sites), str(n_threads), *args], capture_output=True, text=True, env=env, timeout=300)
+
+    for n_sites in N_SITES:
+        for n_inds in ([n for n in N_IND[:9]], N_IND[9:]):
+            blocks, want, ploidies = case(rng, n_sites, n_inds)
+            res = run(n_sites, 3, n_inds, ploidies, blocks)
+            assert res.returncode == 0 and "runtime error" not in res.stderr and "Sanitizer" not in res.stderr, res.stderr[-3000:]
+            got = np.array([[int(line[16 * s : 16 * s + 16], 16) for s in range(n_sites)] for line in res.stdout.splitlines()], dtype=np.uint64)
+            assert np.array_equal(got, want.view(np.uint64)), (n_sites, n_inds)
+            assert same_bits(host_freqs(blocks, n_inds, ploidies, n_sites, 3), want)
+    fields = random_fields(rng, 5000, 129)  # more than one thread
+    res = run(5000, 3, [129], [1], [pack_numpy(fields)])
+    assert res.returncode == 0 and not res.stderr, res.stderr[-3000:]
+    assert np.array_equal(np.array([int(res.stdout[16 * s : 16 * s + 16], 16) for s in range(5000)], dtype=np.uint64), freqs_numpy(fields, 1).view(np.uint64))
+    res = run(3, 1, [3], [0], [pack_numpy(np.zeros((3, 3), dtype=np.uint8))])
+    assert res.returncode == 3 and "ploidy[0] must be positive" in res.stderr and "Sanitizer" not in res.stderr
