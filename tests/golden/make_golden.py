@@ -680,6 +680,14 @@ DD_SEEDED = [
     ("dd_many_src_individuals", 33, 120, 5, 4, [11, 150], 0.02, [2, 2, [2, 1], 2]),
     ("dd_tetraploid", 34, 80, 3, 8, [2], 0.05, [4, 4, [4], 2]),
     ("dd_long", 35, 5000, 4, 3, [2], 0.01, [2, 2, [2], 2]),
+    # source populations whose mean over the individuals is more than one leaf of np.sum's tree: two and three
+    # levels, the seven-level sizes (7689..8191) and past the 8192-element piece; n_ref 7 and n_tgt 3 give the
+    # per-individual differences full mantissas.  The seeds are chosen so that the reference's value differs from a
+    # left-to-right mean AND from the wrong tree that applies (136-element leaves; six levels -- one seed in forty
+    # shows that one, 41..151 do not --; no pieces): tests/test_sum_order_cases_cpu.py asserts it
+    ("dd_src_129_263", 48, 64, 7, 3, [129, 263], 0.05, [2, 2, [2, 2], 2]),
+    ("dd_src_7693", 152, 64, 7, 3, [7693], 0.05, [2, 2, [2], 2]),
+    ("dd_src_8193", 43, 64, 7, 3, [8193], 0.05, [2, 2, [2], 2]),
 ]
 
 
