@@ -21,9 +21,9 @@ INCLUDE = ROOT / "include" if (ROOT / "include" / "saihip.h").exists() else PKG 
 # include/saihip_pgen.h; plink/bed_pack2_host.cpp: .bed rows into the packed2 layout, include/saihip_packed_ingest.h;
 # pgen/pgen_pack2_host.cpp: .pgen records into the packed2 layout, include/saihip_pgen_packed.h; bcf/: the BCF reader,
 # include/saihip_bcf.h; bcf/bcf_feed.cpp: the host side of the BCF route that finds the records on the GPU,
-# include/saihip_bcf_device.h; packed_stats/packed2_freqs_host.cpp: per-site frequencies of packed2 blocks,
+# include/saihip_bcf_device.h; bcf/csi_index.cpp: the .csi index of a BCF file, include/saihip_bcf_index.h; packed_stats/packed2_freqs_host.cpp: per-site frequencies of packed2 blocks,
 # include/saihip_packed_stats.h)
-HOST_UNITS = ["host_core.cpp", "vcf_ingest.cpp", "vcf_stream.cpp", "bgzf_stream.cpp", "narrow.cpp", "text_out.cpp", "plink/plink_index.cpp", "plink/bed_pack2_host.cpp", "eigenstrat/eigenstrat_index.cpp", "pgen/pgen_index.cpp", "pgen/pgen_pack2_host.cpp", "bcf/bcf_index.cpp", "bcf/bcf_feed.cpp", "packed_stats/packed2_freqs_host.cpp"]
+HOST_UNITS = ["host_core.cpp", "vcf_ingest.cpp", "vcf_stream.cpp", "bgzf_stream.cpp", "narrow.cpp", "text_out.cpp", "plink/plink_index.cpp", "plink/bed_pack2_host.cpp", "eigenstrat/eigenstrat_index.cpp", "pgen/pgen_index.cpp", "pgen/pgen_pack2_host.cpp", "bcf/bcf_index.cpp", "bcf/bcf_feed.cpp", "bcf/csi_index.cpp", "packed_stats/packed2_freqs_host.cpp"]
 UNITS = ["core.hip", "site_pass.hip", "site_pass_dd.hip", "packed2.hip", "windows.hip", "single_window.hip", "plan.hip", "fourpop.hip", "dd.hip", "synth.hip", "tokenize.hip", "inflate.hip", "lines.hip", "plink/bed_decode.hip", "plink/bed_pack2.hip", "eigenstrat/geno_decode.hip", "eigenstrat/geno_transpose.hip", "pgen/pgen_decode.hip", "pgen/pgen_pack2.hip", "bcf/bcf_decode.hip", "bcf/bcf_walk.hip", "packed_stats/packed2_freqs.hip", *HOST_UNITS]
 LIB = PKG / "lib" / "libsaihip.so"
 SAN_LIB = LIB.parent / "libsaihost_san.so"
@@ -105,7 +105,7 @@ def build(force: bool = False, sanitize: bool = False) -> None:
     with open(LIB.parent / ".build.lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         headers = [INCLUDE / "saihip.h", INCLUDE / "saihip_plink.h", INCLUDE / "saihip_eigenstrat.h", INCLUDE / "saihip_pgen.h", INCLUDE / "saihip_packed_ingest.h",
-                   INCLUDE / "saihip_pgen_packed.h", INCLUDE / "saihip_bcf.h", INCLUDE / "saihip_bcf_device.h", INCLUDE / "saihip_packed_stats.h",
+                   INCLUDE / "saihip_pgen_packed.h", INCLUDE / "saihip_bcf.h", INCLUDE / "saihip_bcf_device.h", INCLUDE / "saihip_bcf_index.h", INCLUDE / "saihip_packed_stats.h",
                    *sorted(CSRC.glob("*.hpp")), *sorted(CSRC.glob("plink/*.hpp")), *sorted(CSRC.glob("eigenstrat/*.hpp")),
                    *sorted(CSRC.glob("pgen/*.hpp")), *sorted(CSRC.glob("bcf/*.hpp")), *sorted(CSRC.glob("packed_stats/*.hpp"))]
         hipcc = gxx = None
@@ -133,7 +133,7 @@ def build(force: bool = False, sanitize: bool = False) -> None:
         sys.path.insert(0, str(ROOT))
     import sai_amd  # noqa: F401
     import sai_amd.stats  # noqa: F401
-    from sai_amd import _ffi, _ffi_bcf, _ffi_bcf_device, _ffi_eigenstrat, _ffi_packed_ingest, _ffi_packed_stats, _ffi_pgen, _ffi_pgen_packed, _ffi_plink
+    from sai_amd import _ffi, _ffi_bcf, _ffi_bcf_device, _ffi_bcf_index, _ffi_eigenstrat, _ffi_packed_ingest, _ffi_packed_stats, _ffi_pgen, _ffi_pgen_packed, _ffi_plink
 
     _ffi.load()  # every symbol of include/saihip.h resolves
     _ffi_plink.load()  # ... and of include/saihip_plink.h
@@ -143,4 +143,5 @@ def build(force: bool = False, sanitize: bool = False) -> None:
     _ffi_pgen_packed.load()  # ... and of include/saihip_pgen_packed.h
     _ffi_bcf.load()  # ... and of include/saihip_bcf.h
     _ffi_bcf_device.load()  # ... and of include/saihip_bcf_device.h
+    _ffi_bcf_index.load()  # ... and of include/saihip_bcf_index.h
     _ffi_packed_stats.load()  # ... and of include/saihip_packed_stats.h

@@ -7,6 +7,7 @@
 
 #include "bcf_format.hpp"
 #include "bcf_record.hpp"
+#include "csi_index.hpp"
 #include "saihip_bcf_device.h"
 
 static_assert(sizeof(sai_bcf_record_head) == 64, "a record head is 64 bytes");
@@ -46,6 +47,11 @@ struct sai_bcf_feed {
   std::thread reader;
   double read_s = 0.0, header_s = 0.0, select_s = 0.0, wait_s = 0.0;
   int64_t comp_total = 0;
+  // the seek (sai_bcf_feed_open_at, sai_bcf_feed_seek_stats)
+  int64_t header_end_off = 0;  // the file offset behind the last member that holds a byte of the header
+  bool seeked = false;
+  uint64_t seek_v = 0;
+  int64_t file_bytes = 0, n_members = 0;  // members read so far (the header's, inflated on the host, included)
   ~sai_bcf_feed() { if (f) fclose(f); }
 };
 
@@ -69,7 +75,7 @@ int feed_read(sai_bcf_feed* fd) {
     sai_bcf_feed::Batch& bt = fd->batch[b];
     bt.members.clear();
     unsigned char* buf = fd->bufs[b];
-    size_t at = 0, text = 0;
+    size_t at = 0, text = 0, raw = 0;  // raw: the members' bytes in the file, without the padding between them
     const double t0 = now_s();
     // a member is at most 64 KiB: one is started only where a whole one fits
     while (at + 65536 + 4 <= fd->cap) {
@@ -105,6 +111,7 @@ int feed_read(sai_bcf_feed* fd) {
       bt.members.push_back(mem);
       text += isize;
       at += static_cast<size_t>(bsize);
+      raw += static_cast<size_t>(bsize);
       while (at & 3u) buf[at++] = 0;
     }
     bt.comp_bytes = at;
@@ -113,6 +120,8 @@ int feed_read(sai_bcf_feed* fd) {
       std::lock_guard<std::mutex> lk(fd->m);
       fd->read_s += now_s() - t0;
       fd->comp_total += static_cast<int64_t>(at);
+      fd->file_bytes += static_cast<int64_t>(raw);
+      fd->n_members += static_cast<int64_t>(bt.members.size());
       if (!bt.members.empty()) {
         fd->state[b] = 1;
         ++fd->produced;
@@ -174,6 +183,9 @@ bool feed_header(sai_bcf_feed* fd) {
     fd->first_member_off = last_off;
     fd->first_e0 = data_off - last_text;
   }
+  fd->header_end_off = src.next_member_off();
+  fd->file_bytes = src.file_bytes;
+  fd->n_members = src.n_members;
   return true;
 }
 
@@ -299,6 +311,13 @@ int sai_bcf_record_heads_host(const uint8_t* text, int64_t n_bytes, int32_t seg_
 int sai_bcf_feed_open(const char* path, const char* chrom, int64_t start, int64_t end, int32_t n_samples, const char* const* sample_names,
                       const char* anc_bed_path, void* comp0_host, void* comp1_host, int64_t comp_buffer_bytes, int64_t text_batch_bytes,
                       int32_t whole_file, sai_bcf_feed** feed_out) {
+  return sai_bcf_feed_open_at(path, chrom, start, end, n_samples, sample_names, anc_bed_path, comp0_host, comp1_host, comp_buffer_bytes, text_batch_bytes,
+                              whole_file, nullptr, feed_out);
+}
+
+int sai_bcf_feed_open_at(const char* path, const char* chrom, int64_t start, int64_t end, int32_t n_samples, const char* const* sample_names,
+                         const char* anc_bed_path, void* comp0_host, void* comp1_host, int64_t comp_buffer_bytes, int64_t text_batch_bytes,
+                         int32_t whole_file, const sai_bcf_index* index, sai_bcf_feed** feed_out) {
   return guarded("sai_bcf_feed_open", [&]() -> int {
     if (!path || !chrom || !feed_out) return sai_set_error(SAI_ERR_ARG, "NULL argument");
     *feed_out = nullptr;
@@ -324,6 +343,14 @@ int sai_bcf_feed_open(const char* path, const char* chrom, int64_t start, int64_
     fd->sel.start = start;
     fd->sel.stop = end;
     fd->sel.whole_file = whole_file != 0;
+    uint64_t v = 0;
+    if (index && !whole_file && (start >= 0 || end >= 0) && fd->sel.target >= 0 && index->ix.refs.size() <= fd->header.contig.size() &&
+        index->ix.query(fd->sel.target, start, end, &v) == SAI_BCF_INDEX_SEEK && static_cast<int64_t>(v >> 16) >= fd->header_end_off) {
+      fd->first_member_off = static_cast<int64_t>(v >> 16);
+      fd->first_e0 = static_cast<int64_t>(v & 0xFFFFu);
+      fd->seeked = true;
+      fd->seek_v = v;
+    }
     fd->f = fopen(path, "rb");
     if (!fd->f) return SAI_BCF_HOST_ROUTE;
     fd->bufs[0] = static_cast<unsigned char*>(comp0_host);
@@ -462,6 +489,17 @@ int sai_bcf_feed_stats(sai_bcf_feed* fd, double* file_read_s, double* header_inf
   if (select_s) *select_s = fd->select_s;
   if (wait_s) *wait_s = fd->wait_s;
   if (comp_bytes) *comp_bytes = fd->comp_total;
+  return SAI_OK;
+}
+
+int sai_bcf_feed_seek_stats(sai_bcf_feed* fd, int32_t* seeked, uint64_t* voffset, int32_t* contig, int64_t* file_bytes_read, int64_t* members_read) {
+  if (!fd) return sai_set_error(SAI_ERR_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(fd->m);
+  if (seeked) *seeked = fd->seeked ? 1 : 0;
+  if (voffset) *voffset = fd->seek_v;
+  if (contig) *contig = fd->sel.target;
+  if (file_bytes_read) *file_bytes_read = fd->file_bytes;
+  if (members_read) *members_read = fd->n_members;
   return SAI_OK;
 }
 

@@ -26,6 +26,7 @@ struct BgzfSource {
   bool ceof = false;
   double read_s = 0.0, inflate_s = 0.0;  // seconds in fread / in inflate_member (the threads' wall time)
   int64_t inflated_bytes = 0;
+  int64_t file_bytes = 0, n_members = 0;  // the members inflated so far: their bytes in the file, their number
   std::vector<BgzfMember> members;
   BgzfSource(const char* p, int n_threads) : path(p), pool(n_threads), cbuf(size_t(1) << 20) {}
   ~BgzfSource() { if (f) fclose(f); }
@@ -33,6 +34,9 @@ struct BgzfSource {
   BgzfSource& operator=(const BgzfSource&) = delete;
 
   int open() {
+    if (f) fclose(f);  // once more from the start
+    chave = 0;
+    ceof = false;
     f = fopen(path.c_str(), "rb");
     if (!f) return sai_set_error(SAI_ERR_ARG, "cannot open BCF %s", path.c_str());
     unsigned char head[64];
@@ -43,6 +47,16 @@ struct BgzfSource {
     if (bgzf_member_size(head, n, &hlen) <= 0) return sai_set_error(SAI_ERR_ARG, "%s: not a BGZF file", path.c_str());
     if (fseeko(f, 0, SEEK_SET) != 0) return sai_set_error(SAI_ERR_ARG, "seek failed in %s", path.c_str());
     return SAI_OK;
+  }
+
+  // the file offset of the next member fill() will inflate
+  int64_t next_member_off() const { return static_cast<int64_t>(ftello(f)) - static_cast<int64_t>(chave); }
+
+  // fill() goes on with the member at file offset `coffset`
+  bool seek(int64_t coffset) {
+    chave = 0;
+    ceof = false;
+    return fseeko(f, static_cast<off_t>(coffset), SEEK_SET) == 0;
   }
 
   // Appends the inflated bytes of the next members to out[have ..): at least one byte unless the file has ended
@@ -98,6 +112,8 @@ struct BgzfSource {
       pool.run(nt, work);
       inflate_s += now_s() - t0;
       inflated_bytes += static_cast<int64_t>(out_total);
+      file_bytes += static_cast<int64_t>(off);
+      n_members += static_cast<int64_t>(members.size());
       for (char b : bad)
         if (b) return sai_set_error(SAI_ERR_ARG, "%s: BGZF block fails to inflate or its CRC", path.c_str());
       memmove(cbuf.data(), cbuf.data() + off, chave - off);

@@ -5,6 +5,8 @@
 // Plain C++: part of libsaihip and of the sanitizer build of the host units.
 
 #include "bcf_format.hpp"
+#include "bcf_record.hpp"
+#include "csi_index.hpp"
 
 namespace {
 
@@ -33,6 +35,7 @@ struct Walk {
   BcfHeader header;
   std::vector<char> buf;
   size_t lo = 0, have = 0;
+  size_t step = kInflateStep;  // inflated bytes asked of the source at a time
   bool eof = false;
   Walk(const char* p, const char* c, int64_t s, int64_t e, int n_threads, bool whole, bool gt, const AncMap* a)
       : src(p, n_threads), path(p), chrom(c), start(s), stop(e), whole_file(whole), want_gt(gt), anc(a) {}
@@ -46,7 +49,7 @@ struct Walk {
         have -= lo;
         lo = 0;
       }
-      *rc = src.fill(buf, have, std::max(kInflateStep, n - have), &eof);
+      *rc = src.fill(buf, have, std::max(step, n - have), &eof);
       if (*rc) return false;
     }
     return have - lo >= n;
@@ -54,6 +57,9 @@ struct Walk {
 
   int read_header() {
     if (int rc = src.open()) return rc;
+    lo = have = 0;
+    eof = false;
+    header = BcfHeader();
     int rc;
     if (!need(5, &rc)) return rc ? rc : sai_set_error(SAI_ERR_ARG, "%s: the stream ends inside the BCF magic", path.c_str());
     const unsigned char* m = reinterpret_cast<const unsigned char*>(buf.data());
@@ -67,6 +73,25 @@ struct Walk {
     if (int hrc = parse_bcf_header(buf.data() + 9, l_text, path.c_str(), header)) return hrc;
     lo = 9 + l_text;
     return SAI_OK;
+  }
+
+  // Behind read_header(): go on at the virtual offset `v` instead of at the first record, if a record of contig `tid`
+  // can start there (include/saihip_bcf_index.h).  false: nothing of the stream is valid any more -- read_header() again.
+  bool seek(uint64_t v, int32_t tid) {
+    if (!src.seek(static_cast<int64_t>(v >> 16))) return false;
+    lo = have = 0;
+    eof = false;
+    const size_t u = static_cast<size_t>(v & 0xFFFFu);
+    int rc;
+    if (!need(u + 32, &rc)) return false;
+    const uint8_t* t = reinterpret_cast<const uint8_t*>(buf.data());
+    const uint8_t* defined = reinterpret_cast<const uint8_t*>(header.contig_defined.data());
+    if (!bcfrec::is_candidate(t, static_cast<int64_t>(have), static_cast<int64_t>(u), defined, static_cast<int32_t>(header.contig_defined.size()),
+                              static_cast<int32_t>(header.samples.size())))
+      return false;
+    if (static_cast<int32_t>(bcfrec::le32_at(t, static_cast<int64_t>(u) + 8)) != tid) return false;
+    lo = u;
+    return true;
   }
 
   // on_row(row) -> 0 go on, > 0 enough, < 0 a status
@@ -207,6 +232,11 @@ struct sai_bcf_stream {
   // the producer's phases, seconds: complete once the producer has finished (sai_bcf_stream_stats)
   double read_s = 0.0, inflate_s = 0.0, walk_s = 0.0, copy_s = 0.0, wait_s = 0.0;
   int64_t inflated_bytes = 0, staged_bytes = 0;
+  // the seek (sai_bcf_stream_open_at, sai_bcf_stream_seek_stats)
+  const csi::Index* index = nullptr;
+  bool seeked = false;
+  uint64_t seek_v = 0;
+  int64_t file_bytes = 0, n_members = 0;
   struct Batch {
     std::vector<int32_t> pos, len;
     std::vector<uint8_t> flip, width;
@@ -239,7 +269,24 @@ int bcf_stream_run(sai_bcf_stream* st) {
   int64_t staged = 0;
   const bool want_gt = !st->names.empty();
   Walk walk(path, st->chrom.c_str(), st->start, st->end, st->n_threads, false, want_gt, &st->anc);
+  if (st->index) walk.step = 1;  // member by member: what lies behind the header may not be wanted
   if (int rc = walk.read_header()) return rc;
+  walk.step = kInflateStep;
+  if (st->index) {
+    RowSelect aim;
+    aim.aim(walk.header, st->chrom);
+    uint64_t v = 0;
+    if (aim.target >= 0 && st->index->refs.size() <= walk.header.contig.size() &&
+        st->index->query(aim.target, st->start, st->end, &v) == SAI_BCF_INDEX_SEEK && static_cast<int64_t>(v >> 16) >= walk.src.next_member_off()) {
+      if (walk.seek(v, aim.target)) {
+        std::lock_guard<std::mutex> lk(st->m);
+        st->seeked = true;
+        st->seek_v = v;
+      } else if (int rc = walk.read_header()) {  // from the start, as without an index
+        return rc;
+      }
+    }
+  }
   std::vector<int32_t> cols;
   if (int rc = resolve_samples(walk.header, path, st->names, cols)) return rc;
   {
@@ -269,6 +316,8 @@ int bcf_stream_run(sai_bcf_stream* st) {
     st->walk_s = std::max(0.0, now_s() - t_begin - walk.src.read_s - walk.src.inflate_s - copy_s - wait_s);
     st->inflated_bytes = walk.src.inflated_bytes;
     st->staged_bytes = staged;
+    st->file_bytes = walk.src.file_bytes;
+    st->n_members = walk.src.n_members;
   };
   auto publish = [&](int64_t matched) {
     {
@@ -388,6 +437,14 @@ int sai_bcf_scan(const char* path, const char* chrom, int64_t* first_pos, int64_
 int sai_bcf_stream_open(const char* path, const char* chrom, int64_t start, int64_t end, int32_t n_samples,
                         const char* const* sample_names, const int32_t* ploidy, const char* anc_bed_path, int32_t n_threads,
                         void* buffer0_host, void* buffer1_host, int64_t buffer_bytes, sai_bcf_stream** stream_out) {
+  return sai_bcf_stream_open_at(path, chrom, start, end, n_samples, sample_names, ploidy, anc_bed_path, n_threads, buffer0_host, buffer1_host,
+                                buffer_bytes, nullptr, stream_out);
+}
+
+int sai_bcf_stream_open_at(const char* path, const char* chrom, int64_t start, int64_t end, int32_t n_samples,
+                           const char* const* sample_names, const int32_t* ploidy, const char* anc_bed_path, int32_t n_threads,
+                           void* buffer0_host, void* buffer1_host, int64_t buffer_bytes, const sai_bcf_index* index,
+                           sai_bcf_stream** stream_out) {
   return guarded("sai_bcf_stream_open", [&]() -> int {
     if (!path || !chrom || !stream_out) return sai_set_error(SAI_ERR_ARG, "NULL argument");
     *stream_out = nullptr;
@@ -403,6 +460,7 @@ int sai_bcf_stream_open(const char* path, const char* chrom, int64_t start, int6
     st->end = end;
     st->n_threads = n_threads < 1 ? 1 : n_threads;
     if (anc_bed_path) st->anc_path = anc_bed_path;
+    if (index && (start >= 0 || end >= 0)) st->index = &index->ix;
     for (int32_t s = 0; s < n_samples; ++s) {
       st->names.emplace_back(sample_names[s]);
       st->ploidy.push_back(ploidy[s]);
@@ -479,6 +537,17 @@ int sai_bcf_stream_stats(sai_bcf_stream* st, double* file_read_s, double* inflat
   if (wait_s) *wait_s = st->wait_s;
   if (inflated_bytes) *inflated_bytes = st->inflated_bytes;
   if (staged_bytes) *staged_bytes = st->staged_bytes;
+  return SAI_OK;
+}
+
+int sai_bcf_stream_seek_stats(sai_bcf_stream* st, int32_t* seeked, uint64_t* voffset, int64_t* file_bytes_read, int64_t* members_inflated) {
+  if (!st) return sai_set_error(SAI_ERR_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(st->m);
+  if (!st->finished) return sai_set_error(SAI_ERR_ARG, "the producer has not finished yet: read the stream to its end first");
+  if (seeked) *seeked = st->seeked ? 1 : 0;
+  if (voffset) *voffset = st->seek_v;
+  if (file_bytes_read) *file_bytes_read = st->file_bytes;
+  if (members_inflated) *members_inflated = st->n_members;
   return SAI_OK;
 }
 

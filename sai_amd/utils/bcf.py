@@ -16,6 +16,11 @@ bring the arrays to it:
   the record -- into two staging buffers in turn.  It words every error about the file (profiles/bcf_ingest.txt,
   profiles/bcf_gpu_walk.txt).
 
+A read of a region with a current ``<path>.csi`` beside the file begins, on both routes, at the virtual offset that
+index names (``_index_for``; ``sai_bcf_stream_open_at`` / ``sai_bcf_feed_open_at``, bcf/csi_index.cpp); whatever is
+unusual about the index only means that the read walks from the start of the file, as it does without one
+(DESIGN_INGEST.md, "BCF files: a region is a seek"; ``SAI_AMD_BCF_INDEX=0`` switches it off).
+
 The format rules as they are implemented, what of them has not been checked against ``bcftools``, and what is refused
 are in DESIGN_INGEST.md ("BCF files" and "BCF files: members inflated and records found on the GPU").
 
@@ -32,7 +37,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .. import _ffi, _ffi_bcf, _ffi_bcf_device
+from .. import _ffi, _ffi_bcf, _ffi_bcf_device, _ffi_bcf_index
 from ._ingest import check_io, default_threads, pair, region_args, staging
 
 BUFFER_BYTES = 32 << 20  # as the other routes; SAI_AMD_INGEST_BUFFER overrides it
@@ -42,6 +47,7 @@ CARRY_ROOM = 64 << 20  # at most this much of a batch's tail is carried in front
 
 _probed: dict = {}  # (path, size, mtime) -> is a BCF
 _scanned: dict = {}  # (path, size, mtime, chromosome) -> (first, last, n_records_total, n_samples)
+_indexes: dict = {}  # (path, size, mtime, index size, index mtime) -> the sai_bcf_index handle, or None: not usable
 
 
 def _file_key(path):
@@ -71,6 +77,29 @@ def fileset_prefix(path) -> Optional[str]:
 
 def is_fileset(path) -> bool:
     return fileset_prefix(path) is not None
+
+
+def _index_for(path, start, end):
+    """The handle of ``<path>.csi`` for a read with ``start`` or ``end`` given, or None: no region, no index beside
+    the file, ``SAI_AMD_BCF_INDEX=0``, an index older than the file (whole seconds, as for a ``.tbi``) or one that does
+    not parse or fails a check.  None is never an error: the read walks from the start of the file.  Opened once per
+    (path, size, mtime, index size, index mtime) and kept for the life of the process, like the scan results."""
+    if (start is None and end is None) or os.environ.get("SAI_AMD_BCF_INDEX", "1") == "0":
+        return None
+    try:
+        text = os.fspath(path)
+        ist = os.stat(text + ".csi")
+        key = (*_file_key(text), ist.st_size, ist.st_mtime_ns)
+    except OSError:
+        return None
+    if key not in _indexes:
+        handle = None
+        if ist.st_mtime_ns // 10**9 >= key[2] // 10**9:
+            lib, opened = _ffi_bcf_index.load_host(), C.c_void_p()
+            if lib.sai_bcf_index_open(os.fsencode(text + ".csi"), key[1], C.byref(opened)) == 0:
+                handle = opened
+        _indexes[key] = handle
+    return _indexes[key]
 
 
 def _gpu_walk_wanted() -> bool:
@@ -136,13 +165,16 @@ def _cap(buffer_bytes) -> int:
 class _Stream:
     """One ``sai_bcf_stream``: the batches of a region and, once the first has come, the selection."""
 
-    def __init__(self, lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffers, cap):
+    def __init__(self, lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffers, cap, index=None):
         self.lib, self.path, self.chr_name = lib, os.fspath(path), str(chr_name)
         self.samples = list(samples)
         self.ploidies = np.asarray([int(p) for p in ploidies], dtype=np.int32)
         self.handle = C.c_void_p()
         args = region_args(path, chr_name, start, end, samples, ploidies, anc_allele_file, n_threads)
-        check_io(lib, lib.sai_bcf_stream_open(*args, C.c_void_p(buffers[0]), C.c_void_p(buffers[1]), cap, C.byref(self.handle)))
+        if index is None:
+            check_io(lib, lib.sai_bcf_stream_open(*args, C.c_void_p(buffers[0]), C.c_void_p(buffers[1]), cap, C.byref(self.handle)))
+        else:
+            check_io(lib, lib.sai_bcf_stream_open_at(*args, C.c_void_p(buffers[0]), C.c_void_p(buffers[1]), cap, index, C.byref(self.handle)))
         self.cols = None  # int32 [n slots]: the sample column of every slot
         self.n_cols = 0
         self.first_col = self.uniform_ploidy = -1
@@ -185,7 +217,16 @@ class _Stream:
         n = [C.c_int64() for _ in range(2)]
         check_io(self.lib, self.lib.sai_bcf_stream_stats(self.handle, *[C.byref(x) for x in t], *[C.byref(x) for x in n]))
         names = ("file_read", "inflate", "walk", "copy_to_staging", "wait_for_buffer")
-        return {**{k: float(x.value) for k, x in zip(names, t)}, "inflated_bytes": int(n[0].value), "staged_bytes": int(n[1].value)}
+        return {**{k: float(x.value) for k, x in zip(names, t)}, "inflated_bytes": int(n[0].value), "staged_bytes": int(n[1].value),
+                "seek": self.seek()}  # fmt: skip
+
+    def seek(self) -> dict:
+        """Whether the producer began at a virtual offset of the index, which one, and the bytes of the file and the
+        members it inflated (``sai_bcf_stream_seek_stats``), once the stream is read to its end."""
+        lib = _ffi_bcf_index.load_host()
+        made, v, n_bytes, n_members = C.c_int32(), C.c_uint64(), C.c_int64(), C.c_int64()
+        check_io(lib, lib.sai_bcf_stream_seek_stats(self.handle, C.byref(made), C.byref(v), C.byref(n_bytes), C.byref(n_members)))
+        return {"made": bool(made.value), "voffset": int(v.value), "file_bytes": int(n_bytes.value), "members": int(n_members.value)}
 
     def counts(self) -> tuple:
         """(rows matched before polarisation, entries of the ancestral-allele table) of the finished walk."""
@@ -219,16 +260,29 @@ class _Stream:
 
 def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[int], start: Optional[int] = None,
                 end: Optional[int] = None, anc_allele_file: Optional[str] = None, n_threads: Optional[int] = None,
-                buffer_bytes: Optional[int] = None):  # fmt: skip
+                buffer_bytes: Optional[int] = None, trace: Optional[dict] = None):  # fmt: skip
     """(pos int32 [n], dosage int8 [n][len(samples)], n_matched, n_anc_entries) for one region, decoded on the
-    host (``sai_bcf_decode_host``): the ``SAI_AMD_INGEST=host`` route and the yardstick of the kernel."""
+    host (``sai_bcf_decode_host``): the ``SAI_AMD_INGEST=host`` route and the yardstick of the kernel.  With a region
+    and a current ``<path>.csi`` the stream begins where the index says (``_index_for``); a read that began there and
+    fails is read again from the start of the file, so the index never words an error.  ``trace`` (a dict) gets the
+    stream's stats, ``seek`` among them."""
+    index = _index_for(path, start, end)
+    if index is not None:
+        try:
+            return _load_dosage(path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes, trace, index)
+        except ValueError:
+            pass
+    return _load_dosage(path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes, trace, None)
+
+
+def _load_dosage(path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes, trace, index):
     lib = _ffi_bcf.load_host()
     n_threads = n_threads or default_threads()
     cap, n = _cap(buffer_bytes), len(samples)
     bufs = [np.empty(cap, dtype=np.uint8) for _ in range(2)]
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     pos_parts, dos_parts = [], []
-    with _Stream(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, [b.ctypes.data for b in bufs], cap) as stream:
+    with _Stream(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, [b.ctypes.data for b in bufs], cap, index) as stream:
         while True:
             got = stream.next()
             if got is None:
@@ -243,6 +297,8 @@ def load_dosage(path, chr_name: str, samples: Sequence[str], ploidies: Sequence[
                 stream.raise_flagged(bufs[b], n_bytes, pos, flip, off, width, length, status)
             dos_parts.append(dos)
         n_matched, n_anc = stream.counts()
+        if trace is not None:
+            trace.update(stream.stats())
     pos = np.concatenate(pos_parts) if pos_parts else np.zeros(0, dtype=np.int32)
     dos = np.concatenate(dos_parts) if dos_parts else np.zeros((0, n), dtype=np.int8)
     return pos, dos, n_matched, n_anc
@@ -274,22 +330,36 @@ def load_dosage_device(eng, path, chr_name: str, samples: Sequence[str], ploidie
     ``load_dosage`` with the result left in HBM.  The GPU route (``_load_device_walk``) unless ``SAI_AMD_GPU_INFLATE=0``,
     in batches of ``SAI_AMD_INFLATE_BATCH`` inflated bytes (default: by the file's size,
     as for a bgzip VCF); where that route hands the read over, and otherwise, the host route (``_load_host_inflate``).
-    ``trace`` (a dict) gets ``route`` = ``"device"`` / ``"host"`` and the route's seconds per phase."""
+    ``trace`` (a dict) gets ``route`` = ``"device"`` / ``"host"``, the route's seconds per phase and ``seek``: whether
+    the read began at a virtual offset of ``<path>.csi`` (``_index_for``), which one, and the bytes of the file read.
+    A read that began there and does not come through -- on either route -- is made again from the start of the file
+    on the same route, exactly as without an index."""
+    index = _index_for(path, start, end)
+    attempts = [index, None] if index is not None else [None]
     if _gpu_walk_wanted():
         icap = int(os.environ.get("SAI_AMD_INFLATE_BATCH", 0)) or _inflate_batch(path)
-        try:
-            got = _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, icap, trace)
-            if trace is not None:
-                trace["route"] = "device"
-            return got[:4]
-        except _HostRoute:
-            pass
+        for ix in attempts:
+            try:
+                got = _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, icap, trace, index=ix)
+                if trace is not None:
+                    trace["route"] = "device"
+                return got[:4]
+            except _HostRoute:
+                pass
+            except ValueError:
+                if ix is None:
+                    raise
     if trace is not None:
         trace["route"] = "host"
+    if index is not None:
+        try:
+            return _load_host_inflate(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes, trace, index)
+        except ValueError:
+            pass
     return _load_host_inflate(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes, trace)
 
 
-def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, icap, trace, whole_file=False):
+def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, icap, trace, whole_file=False, index=None):
     """(pos, dosage, n_matched, n_anc, (first, last, records seen, samples of the file)) through the GPU route, or
     ``_HostRoute``.  Per batch, on a side stream: the compressed members and their table go to the device; ``sai_inflate_bgzf`` writes their
     text behind the carry of the batch before; ``sai_bcf_chain_segments`` summarises every segment and the summaries
@@ -297,7 +367,13 @@ def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_al
     ``sai_bcf_feed_select``; the row tables go up and ``sai_bcf_decode`` reads the GT arrays out of the text.  The
     bytes from the first incomplete record on are copied, device to device, to the front of the other text buffer.
     The feed's thread reads batch k + 1 from the file meanwhile.  With ``trace["serial"]`` the stream is synchronised
-    behind every step, so ``h2d``, ``inflate_gpu``, ``walk_gpu`` and ``decode`` are timed on their own."""
+    behind every step, so ``h2d``, ``inflate_gpu``, ``walk_gpu`` and ``decode`` are timed on their own.
+
+    With ``index`` (``sai_bcf_feed_open_at``) the first batch's members start at the ``coffset`` the index names and
+    the stitch's known entry is its ``uoffset``.  The text in front of it holds the end of earlier records, whose
+    chains run into ``uoffset``, so it is cleared first: the stitch wants its entry to be the head of a chain.  An
+    entry that is no record start, a first record of another contig or a broken chain is ``_HostRoute("seek")`` or the
+    stitch's own verdict, and the caller reads from the start of the file."""
     import time
 
     import torch
@@ -318,11 +394,18 @@ def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_al
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     names = (C.c_char_p * n)(*[s.encode() for s in samples])
     feed = C.c_void_p()
-    rc = lib.sai_bcf_feed_open(os.fsencode(text_path), str(chr_name).encode(), -1 if start is None else int(start), -1 if end is None else int(end),
-                               n, names, os.fsencode(anc_allele_file) if anc_allele_file else None, C.c_void_p(pinned[0].data_ptr()),
-                               C.c_void_p(pinned[1].data_ptr()), comp_cap, icap, int(whole_file), C.byref(feed))  # fmt: skip
+    ilib = _ffi_bcf_index.load()
+    rc = ilib.sai_bcf_feed_open_at(os.fsencode(text_path), str(chr_name).encode(), -1 if start is None else int(start), -1 if end is None else int(end),
+                                   n, names, os.fsencode(anc_allele_file) if anc_allele_file else None, C.c_void_p(pinned[0].data_ptr()),
+                                   C.c_void_p(pinned[1].data_ptr()), comp_cap, icap, int(whole_file), index, C.byref(feed))  # fmt: skip
     if rc:
         raise _HostRoute("open")
+
+    def seek_stats():
+        made, v, contig, n_file_bytes, n_members = C.c_int32(), C.c_uint64(), C.c_int32(), C.c_int64(), C.c_int64()
+        ilib.sai_bcf_feed_seek_stats(feed, C.byref(made), C.byref(v), C.byref(contig), C.byref(n_file_bytes), C.byref(n_members))
+        return {"made": bool(made.value), "voffset": int(v.value), "file_bytes": int(n_file_bytes.value), "members": int(n_members.value)}, int(contig.value)
+
     serial = trace is not None and trace.get("serial")
     laps = {}
 
@@ -349,6 +432,9 @@ def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_al
             d_cols = torch.from_numpy(cols).to(eng.device) if n and first_col < 0 else None
             d_pl = torch.from_numpy(pl).to(eng.device) if n and uniform == 0 else None
         carry, done = 0, False
+        seek, contig = seek_stats()
+        unchecked = seek["made"]  # the first record from the seek on has to be one of the chromosome's
+        first_batch = True
         while not done:
             b, n_comp, n_members, n_text, e0, end_of_file = C.c_int32(), C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32()
             members = C.c_void_p()
@@ -360,6 +446,10 @@ def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_al
             b, n_comp, nm, n_text = int(b.value), int(n_comp.value), int(n_members.value), int(n_text.value)
             n_bytes = carry + n_text  # at most text_cap: carry <= room, and a batch is icap bytes or one member
             entry = 0 if carry else int(e0.value)
+            clear = entry if seek["made"] and first_batch else 0
+            first_batch = False
+            if clear > n_text:
+                raise _HostRoute("seek")  # uoffset lies behind its member
             table = np.ctypeslib.as_array(C.cast(members, C.POINTER(C.c_uint8)), shape=(nm * 32,)).copy()
             n_seg = -(-n_bytes // seg_bytes)
             text = text_dev[b]
@@ -372,6 +462,8 @@ def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_al
                 _ffi.check(lib.sai_inflate_bgzf(eng.ctx, C.c_void_p(comp_dev[b].data_ptr()), n_comp, C.c_void_p(d_table.data_ptr()), nm,
                                                 C.c_void_p(text.data_ptr() + carry), n_text, C.c_void_p(d_member_status.data_ptr()),
                                                 C.c_void_p(side.cuda_stream)))  # fmt: skip
+                if clear:
+                    text[:clear].zero_()
                 t1 = lap("inflate_gpu", t1)
                 d_chains = torch.empty((n_seg * max_heads * 16,), dtype=torch.uint8, device=eng.device)
                 d_info = torch.empty((n_seg,), dtype=torch.int32, device=eng.device)
@@ -399,6 +491,10 @@ def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_al
                                                         C.c_void_p(d_heads.data_ptr()), C.c_void_p(side.cuda_stream)))  # fmt: skip
                     heads = d_heads.cpu().numpy().view(_ffi_bcf_device.HEAD)
                 t1 = lap("walk_gpu", t1)
+            if unchecked and n_records:
+                if int(heads[0]["chrom"]) != contig:
+                    raise _HostRoute("seek")
+                unchecked = False
             n_rows, sel_done, verdict = C.c_int64(), C.c_int32(), C.c_int32()
             tabs = [C.c_void_p() for _ in range(5)]
             check_io(lib, lib.sai_bcf_feed_select(feed, ptr(heads), n_records, C.byref(n_rows), *[C.byref(t) for t in tabs], C.byref(sel_done),
@@ -441,7 +537,7 @@ def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_al
             comp_bytes = C.c_int64()
             lib.sai_bcf_feed_stats(feed, *[C.byref(x) for x in t], C.byref(comp_bytes))
             trace.update({k: float(x.value) for k, x in zip(("file_read", "header_inflate", "select", "wait_for_buffer"), t)})
-            trace.update(laps, comp_bytes=int(comp_bytes.value))
+            trace.update(laps, comp_bytes=int(comp_bytes.value), seek=seek_stats()[0])
     finally:
         lib.sai_bcf_feed_close(feed)
         side.synchronize()  # also on an error: the staging buffers are reused by the next call
@@ -453,7 +549,7 @@ def _load_device_walk(eng, path, chr_name, samples, ploidies, start, end, anc_al
     return pos, dos, n_matched, n_anc, (first, last, n_seen, n_cols)
 
 
-def _load_host_inflate(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes, trace):
+def _load_host_inflate(eng, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes, trace, index=None):
     """The host route of ``load_dosage_device``.  The loop of ``device_vcf.load_dosage_device``: the producer thread
     fills one pinned buffer while the other one is copied on a side stream and decoded behind the copy; the producer
     may refill a buffer once its copy has left it.  A row the kernel flags is handed to the host route, which raises
@@ -476,7 +572,7 @@ def _load_host_inflate(eng, path, chr_name, samples, ploidies, start, end, anc_a
     pos_parts, outs, stats, tables = [], [], [], [None, None]
     cols_dev = ploidy_dev = None  # only where the promises of the fast path do not hold
     try:
-        with _Stream(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, [t.data_ptr() for t in pinned], cap) as stream:
+        with _Stream(lib, path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, [t.data_ptr() for t in pinned], cap, index) as stream:
             copied = None
             while True:
                 if copied is not None:
@@ -523,7 +619,7 @@ def _load_host_inflate(eng, path, chr_name, samples, ploidies, start, end, anc_a
     finally:
         side.synchronize()  # also on an error: the staging buffers are reused by the next call
     if stats and bool(torch.cat(stats).any()):
-        load_dosage(path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes)
+        _load_dosage(path, chr_name, samples, ploidies, start, end, anc_allele_file, n_threads, buffer_bytes, None, None)
         raise ValueError(f"{os.fspath(path)}: the GPU decoder flagged a row the host reader accepts")
     current.wait_stream(side)
     pos = np.concatenate(pos_parts) if pos_parts else np.zeros(0, dtype=np.int32)

@@ -25,7 +25,7 @@ def build_library() -> None:
         dst = ROOT / "sai_amd" / "include"
         dst.mkdir(exist_ok=True)
         for header in ("saihip.h", "saihip_plink.h", "saihip_eigenstrat.h", "saihip_pgen.h", "saihip_packed_ingest.h", "saihip_pgen_packed.h", "saihip_bcf.h",
-                       "saihip_bcf_device.h", "saihip_packed_stats.h"):
+                       "saihip_bcf_device.h", "saihip_bcf_index.h", "saihip_packed_stats.h"):
             shutil.copy2(ROOT / "include" / header, dst / header)  # travel as package data
     finally:
         sys.path.remove(str(ROOT))
