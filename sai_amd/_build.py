@@ -16,15 +16,63 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 # the public header: include/ at the repository root, or the copy an installed package carries
 INCLUDE = ROOT / "include" if (ROOT / "include" / "saihip.h").exists() else PKG / "include"
-# plain C++: also built alone under the sanitizers (plink/: the PLINK 1 fileset reader, include/saihip_plink.h;
-# eigenstrat/: the EIGENSOFT fileset reader, include/saihip_eigenstrat.h; pgen/: the PLINK 2 fileset reader,
-# include/saihip_pgen.h; plink/bed_pack2_host.cpp: .bed rows into the packed2 layout, include/saihip_packed_ingest.h;
-# pgen/pgen_pack2_host.cpp: .pgen records into the packed2 layout, include/saihip_pgen_packed.h; bcf/: the BCF reader,
-# include/saihip_bcf.h; bcf/bcf_feed.cpp: the host side of the BCF route that finds the records on the GPU,
-# include/saihip_bcf_device.h; bcf/csi_index.cpp: the .csi index of a BCF file, include/saihip_bcf_index.h; packed_stats/packed2_freqs_host.cpp: per-site frequencies of packed2 blocks,
-# include/saihip_packed_stats.h)
-HOST_UNITS = ["host_core.cpp", "vcf_ingest.cpp", "vcf_stream.cpp", "bgzf_stream.cpp", "narrow.cpp", "text_out.cpp", "plink/plink_index.cpp", "plink/bed_pack2_host.cpp", "eigenstrat/eigenstrat_index.cpp", "pgen/pgen_index.cpp", "pgen/pgen_pack2_host.cpp", "bcf/bcf_index.cpp", "bcf/bcf_feed.cpp", "bcf/csi_index.cpp", "packed_stats/packed2_freqs_host.cpp"]
-UNITS = ["core.hip", "site_pass.hip", "site_pass_dd.hip", "packed2.hip", "windows.hip", "single_window.hip", "plan.hip", "fourpop.hip", "dd.hip", "synth.hip", "tokenize.hip", "inflate.hip", "lines.hip", "plink/bed_decode.hip", "plink/bed_pack2.hip", "eigenstrat/geno_decode.hip", "eigenstrat/geno_transpose.hip", "pgen/pgen_decode.hip", "pgen/pgen_pack2.hip", "bcf/bcf_decode.hip", "bcf/bcf_walk.hip", "packed_stats/packed2_freqs.hip", *HOST_UNITS]
+# every header a family of entry points has: saihip.h, and one saihip_X.h per sai_amd/_ffi_X.py
+PUBLIC_HEADERS = sorted(INCLUDE.glob("saihip*.h"))
+# plain C++: built with g++, and also alone under the sanitizers.  The order is the link order.
+HOST_UNITS = [
+    "host_core.cpp",
+    "vcf_ingest.cpp",
+    "vcf_stream.cpp",
+    "bgzf_stream.cpp",
+    "narrow.cpp",
+    "text_out.cpp",
+    "plink/plink_index.cpp",
+    "plink/bed_pack2_host.cpp",
+    "eigenstrat/eigenstrat_index.cpp",
+    "pgen/pgen_index.cpp",
+    "pgen/pgen_pack2_host.cpp",
+    "bcf/bcf_index.cpp",
+    "bcf/bcf_feed.cpp",
+    "bcf/csi_index.cpp",
+    "packed_stats/packed2_freqs_host.cpp",
+]
+UNITS = [
+    "core.hip",
+    "site_pass.hip",
+    "site_pass_dd.hip",
+    "packed2.hip",
+    "windows.hip",
+    "single_window.hip",
+    "plan.hip",
+    "fourpop.hip",
+    "dd.hip",
+    "synth.hip",
+    "tokenize.hip",
+    "inflate.hip",
+    "lines.hip",
+    "plink/bed_decode.hip",
+    "plink/bed_pack2.hip",
+    "eigenstrat/geno_decode.hip",
+    "eigenstrat/geno_transpose.hip",
+    "pgen/pgen_decode.hip",
+    "pgen/pgen_pack2.hip",
+    "bcf/bcf_decode.hip",
+    "bcf/bcf_walk.hip",
+    "packed_stats/packed2_freqs.hip",
+    *HOST_UNITS,
+]
+
+
+def check_object_names(units) -> None:
+    """An object file is named by its unit's stem alone: two units of one name in two directories would
+    overwrite each other's object without a word."""
+    stems = [Path(u).stem for u in units]
+    twice = sorted(u for u in units if stems.count(Path(u).stem) > 1)
+    if twice:
+        raise RuntimeError(f"units with the same object name: {' '.join(twice)}")
+
+
+check_object_names(UNITS)
 LIB = PKG / "lib" / "libsaihip.so"
 SAN_LIB = LIB.parent / "libsaihost_san.so"
 OBJ = LIB.parent / "obj"
@@ -52,6 +100,19 @@ def _stale(target: Path, sources) -> bool:
         return True
     t = target.stat().st_mtime
     return any(Path(s).stat().st_mtime > t for s in sources)
+
+
+def staleness_inputs() -> list:
+    """The headers every object depends on: the public ones and each .hpp under csrc, at any depth."""
+    return [*PUBLIC_HEADERS, *sorted(CSRC.rglob("*.hpp"))]
+
+
+def _max_jobs() -> int:
+    """Compile jobs at a time: the CPUs of the machine, or fewer where MAX_JOBS says that this process may
+    use fewer than the machine has."""
+    cpus = os.cpu_count() or 1
+    cap = os.environ.get("MAX_JOBS", "")
+    return min(cpus, int(cap)) if cap.isdigit() and int(cap) > 0 else cpus
 
 
 def _run(cmd) -> None:
@@ -104,10 +165,7 @@ def build(force: bool = False, sanitize: bool = False) -> None:
     OBJ.mkdir(parents=True, exist_ok=True)
     with open(LIB.parent / ".build.lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
-        headers = [INCLUDE / "saihip.h", INCLUDE / "saihip_plink.h", INCLUDE / "saihip_eigenstrat.h", INCLUDE / "saihip_pgen.h", INCLUDE / "saihip_packed_ingest.h",
-                   INCLUDE / "saihip_pgen_packed.h", INCLUDE / "saihip_bcf.h", INCLUDE / "saihip_bcf_device.h", INCLUDE / "saihip_bcf_index.h", INCLUDE / "saihip_packed_stats.h",
-                   *sorted(CSRC.glob("*.hpp")), *sorted(CSRC.glob("plink/*.hpp")), *sorted(CSRC.glob("eigenstrat/*.hpp")),
-                   *sorted(CSRC.glob("pgen/*.hpp")), *sorted(CSRC.glob("bcf/*.hpp")), *sorted(CSRC.glob("packed_stats/*.hpp"))]
+        headers = staleness_inputs()
         hipcc = gxx = None
         jobs = []
         for unit in UNITS:
@@ -120,7 +178,7 @@ def build(force: bool = False, sanitize: bool = False) -> None:
                 else:
                     jobs.append([hipcc, *HIPCC_FLAGS, f"-I{INCLUDE}", "-c", str(src), "-o", str(obj)])
         if jobs:
-            with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as pool:
+            with ThreadPoolExecutor(max_workers=min(len(jobs), _max_jobs())) as pool:
                 list(pool.map(_run, jobs))
         objs = [OBJ / (Path(u).stem + ".o") for u in UNITS]
         if force or _stale(LIB, objs):
@@ -133,15 +191,7 @@ def build(force: bool = False, sanitize: bool = False) -> None:
         sys.path.insert(0, str(ROOT))
     import sai_amd  # noqa: F401
     import sai_amd.stats  # noqa: F401
-    from sai_amd import _ffi, _ffi_bcf, _ffi_bcf_device, _ffi_bcf_index, _ffi_eigenstrat, _ffi_packed_ingest, _ffi_packed_stats, _ffi_pgen, _ffi_pgen_packed, _ffi_plink
+    from sai_amd._binding import family_modules
 
-    _ffi.load()  # every symbol of include/saihip.h resolves
-    _ffi_plink.load()  # ... and of include/saihip_plink.h
-    _ffi_eigenstrat.load()  # ... and of include/saihip_eigenstrat.h
-    _ffi_pgen.load()  # ... and of include/saihip_pgen.h
-    _ffi_packed_ingest.load()  # ... and of include/saihip_packed_ingest.h
-    _ffi_pgen_packed.load()  # ... and of include/saihip_pgen_packed.h
-    _ffi_bcf.load()  # ... and of include/saihip_bcf.h
-    _ffi_bcf_device.load()  # ... and of include/saihip_bcf_device.h
-    _ffi_bcf_index.load()  # ... and of include/saihip_bcf_index.h
-    _ffi_packed_stats.load()  # ... and of include/saihip_packed_stats.h
+    for module in family_modules():  # every symbol of include/saihip.h and of each include/saihip_X.h resolves
+        module.load()

@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi
+from ._binding import extension
 
 SAI_BCF_DEVICE_ABI_VERSION = 1
 SAI_BCF_MAX_HEADS = 8
@@ -59,30 +59,5 @@ SIGNATURES = {
 HOST_SYMBOLS = tuple(n for n in SIGNATURES if n not in ("sai_bcf_chain_segments", "sai_bcf_record_heads"))
 
 
-def _attach(lib: C.CDLL, names) -> C.CDLL:
-    if getattr(lib, "_sai_bcf_device_attached", None) == tuple(names):
-        return lib
-    for name in names:
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise RuntimeError(f"{name} is missing from libsaihip: the library was built without sai_amd/csrc/bcf/bcf_walk.hip or "
-                               "bcf_feed.cpp (rebuild it: `python -c 'import __graft_entry__ as g; g.build()'`)") from None  # fmt: skip
-        fn.restype, fn.argtypes = SIGNATURES[name]
-    if lib.sai_bcf_device_abi_version() != SAI_BCF_DEVICE_ABI_VERSION:
-        raise RuntimeError(f"libsaihip: BCF device ABI {lib.sai_bcf_device_abi_version()} != expected {SAI_BCF_DEVICE_ABI_VERSION}")
-    lib._sai_bcf_device_attached = tuple(names)
-    return lib
-
-
-def load() -> C.CDLL:
-    """``_ffi.load()`` with every prototype of saihip_bcf_device.h declared."""
-    return _attach(_ffi.load(), tuple(SIGNATURES))
-
-
-def load_host() -> C.CDLL:
-    """``_ffi.load_host()`` with the host-only prototypes declared (the sanitizer build has no kernel)."""
-    lib = _ffi.load_host()
-    if lib is _ffi._lib:
-        return load()
-    return _attach(lib, HOST_SYMBOLS)
+load, load_host = extension("BCF device", "saihip_bcf_device.h", "sai_bcf_device_abi_version", SAI_BCF_DEVICE_ABI_VERSION,
+                            SIGNATURES, HOST_SYMBOLS, built_from="bcf/bcf_walk.hip or bcf_feed.cpp")  # fmt: skip

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from . import _ffi
+from ._binding import extension
 
 SAI_BCF_INDEX_ABI_VERSION = 1
 SAI_BCF_INDEX_NONE = 0
@@ -40,27 +40,5 @@ SIGNATURES = {
 HOST_SYMBOLS = tuple(SIGNATURES)
 
 
-def _attach(lib: C.CDLL) -> C.CDLL:
-    if getattr(lib, "_sai_bcf_index_attached", False):
-        return lib
-    for name in SIGNATURES:
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise RuntimeError(f"{name} is missing from libsaihip: the library was built without sai_amd/csrc/bcf/csi_index.cpp "
-                               "(rebuild it: `python -c 'import __graft_entry__ as g; g.build()'`)") from None  # fmt: skip
-        fn.restype, fn.argtypes = SIGNATURES[name]
-    if lib.sai_bcf_index_abi_version() != SAI_BCF_INDEX_ABI_VERSION:
-        raise RuntimeError(f"libsaihip: BCF index ABI {lib.sai_bcf_index_abi_version()} != expected {SAI_BCF_INDEX_ABI_VERSION}")
-    lib._sai_bcf_index_attached = True
-    return lib
-
-
-def load() -> C.CDLL:
-    """``_ffi.load()`` with every prototype of saihip_bcf_index.h declared."""
-    return _attach(_ffi.load())
-
-
-def load_host() -> C.CDLL:
-    """``_ffi.load_host()`` with the same prototypes declared: the sanitizer build has all of them."""
-    return _attach(_ffi.load_host())
+load, load_host = extension("BCF index", "saihip_bcf_index.h", "sai_bcf_index_abi_version", SAI_BCF_INDEX_ABI_VERSION, SIGNATURES,
+                            HOST_SYMBOLS, built_from="bcf/csi_index.cpp")  # fmt: skip

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from . import _ffi
+from ._binding import extension
 
 SAI_PACKED_INGEST_ABI_VERSION = 1
 
@@ -27,31 +27,5 @@ SIGNATURES = {
 # entry points that never touch the GPU (plink/bed_pack2_host.cpp)
 HOST_SYMBOLS = tuple(n for n in SIGNATURES if n != "sai_bed_pack2")
 
-
-def _attach(lib: C.CDLL, names) -> C.CDLL:
-    if getattr(lib, "_sai_packed_ingest_attached", None) == tuple(names):
-        return lib
-    for name in names:
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise RuntimeError(f"{name} is missing from libsaihip: the library was built without sai_amd/csrc/plink/bed_pack2* "
-                               "(rebuild it: `python -c 'import __graft_entry__ as g; g.build()'`)") from None  # fmt: skip
-        fn.restype, fn.argtypes = SIGNATURES[name]
-    if lib.sai_packed_ingest_abi_version() != SAI_PACKED_INGEST_ABI_VERSION:
-        raise RuntimeError(f"libsaihip: packed-ingest ABI {lib.sai_packed_ingest_abi_version()} != expected {SAI_PACKED_INGEST_ABI_VERSION}")
-    lib._sai_packed_ingest_attached = tuple(names)
-    return lib
-
-
-def load() -> C.CDLL:
-    """``_ffi.load()`` with every prototype of saihip_packed_ingest.h declared."""
-    return _attach(_ffi.load(), tuple(SIGNATURES))
-
-
-def load_host() -> C.CDLL:
-    """``_ffi.load_host()`` with the host-only prototypes declared (the sanitizer build has no kernel)."""
-    lib = _ffi.load_host()
-    if lib is _ffi._lib:
-        return load()
-    return _attach(lib, HOST_SYMBOLS)
+load, load_host = extension("packed-ingest", "saihip_packed_ingest.h", "sai_packed_ingest_abi_version", SAI_PACKED_INGEST_ABI_VERSION, SIGNATURES, HOST_SYMBOLS,
+                            built_from="plink/bed_pack2*")  # fmt: skip

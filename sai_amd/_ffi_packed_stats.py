@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _ffi
+from ._binding import extension
 
 SAI_PACKED_STATS_ABI_VERSION = 1
 SAI_PACKED_FREQ_POPS = 9  # ref, tgt, SAI_FUSED_SRC sources, outgroup
@@ -28,31 +29,5 @@ SIGNATURES = {
 # entry points that never touch the GPU (packed_stats/packed2_freqs_host.cpp)
 HOST_SYMBOLS = tuple(n for n in SIGNATURES if n != "sai_packed2_site_freqs")
 
-
-def _attach(lib: C.CDLL, names) -> C.CDLL:
-    if getattr(lib, "_sai_packed_stats_attached", None) == tuple(names):
-        return lib
-    for name in names:
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise RuntimeError(f"{name} is missing from libsaihip: the library was built without sai_amd/csrc/packed_stats/packed2_freqs* "
-                               "(rebuild it: `python -c 'import __graft_entry__ as g; g.build()'`)") from None  # fmt: skip
-        fn.restype, fn.argtypes = SIGNATURES[name]
-    if lib.sai_packed_stats_abi_version() != SAI_PACKED_STATS_ABI_VERSION:
-        raise RuntimeError(f"libsaihip: packed-stats ABI {lib.sai_packed_stats_abi_version()} != expected {SAI_PACKED_STATS_ABI_VERSION}")
-    lib._sai_packed_stats_attached = tuple(names)
-    return lib
-
-
-def load() -> C.CDLL:
-    """``_ffi.load()`` with every prototype of saihip_packed_stats.h declared."""
-    return _attach(_ffi.load(), tuple(SIGNATURES))
-
-
-def load_host() -> C.CDLL:
-    """``_ffi.load_host()`` with the host-only prototypes declared (the sanitizer build has no kernel)."""
-    lib = _ffi.load_host()
-    if lib is _ffi._lib:
-        return load()
-    return _attach(lib, HOST_SYMBOLS)
+load, load_host = extension("packed-stats", "saihip_packed_stats.h", "sai_packed_stats_abi_version", SAI_PACKED_STATS_ABI_VERSION, SIGNATURES, HOST_SYMBOLS,
+                            built_from="packed_stats/packed2_freqs*")  # fmt: skip

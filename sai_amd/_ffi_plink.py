@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from . import _ffi
+from ._binding import extension
 
 SAI_PLINK_ABI_VERSION = 1
 SAI_PLINK_STATUS_BAD_INDEX = 0x7FFFFFFF
@@ -36,30 +36,5 @@ SIGNATURES = {
 HOST_SYMBOLS = tuple(n for n in SIGNATURES if n != "sai_plink_decode")
 
 
-def _attach(lib: C.CDLL, names) -> C.CDLL:
-    if getattr(lib, "_sai_plink_attached", None) == tuple(names):
-        return lib
-    for name in names:
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise RuntimeError(f"{name} is missing from libsaihip: the library was built without sai_amd/csrc/plink "
-                               "(rebuild it: `python -c 'import __graft_entry__ as g; g.build()'`)") from None  # fmt: skip
-        fn.restype, fn.argtypes = SIGNATURES[name]
-    if lib.sai_plink_abi_version() != SAI_PLINK_ABI_VERSION:
-        raise RuntimeError(f"libsaihip: PLINK ABI {lib.sai_plink_abi_version()} != expected {SAI_PLINK_ABI_VERSION}")
-    lib._sai_plink_attached = tuple(names)
-    return lib
-
-
-def load() -> C.CDLL:
-    """``_ffi.load()`` with every prototype of saihip_plink.h declared."""
-    return _attach(_ffi.load(), tuple(SIGNATURES))
-
-
-def load_host() -> C.CDLL:
-    """``_ffi.load_host()`` with the host-only prototypes declared (the sanitizer build has no kernel)."""
-    lib = _ffi.load_host()
-    if lib is _ffi._lib:
-        return load()
-    return _attach(lib, HOST_SYMBOLS)
+load, load_host = extension("PLINK", "saihip_plink.h", "sai_plink_abi_version", SAI_PLINK_ABI_VERSION, SIGNATURES, HOST_SYMBOLS,
+                            built_from="plink")  # fmt: skip

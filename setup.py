@@ -24,9 +24,8 @@ def build_library() -> None:
         _build.build()
         dst = ROOT / "sai_amd" / "include"
         dst.mkdir(exist_ok=True)
-        for header in ("saihip.h", "saihip_plink.h", "saihip_eigenstrat.h", "saihip_pgen.h", "saihip_packed_ingest.h", "saihip_pgen_packed.h", "saihip_bcf.h",
-                       "saihip_bcf_device.h", "saihip_bcf_index.h", "saihip_packed_stats.h"):
-            shutil.copy2(ROOT / "include" / header, dst / header)  # travel as package data
+        for header in _build.PUBLIC_HEADERS:
+            shutil.copy2(header, dst / header.name)  # travel as package data
     finally:
         sys.path.remove(str(ROOT))
 
@@ -44,11 +43,8 @@ class DevelopWithLibrary(develop):
 
 
 # on top of the table in pyproject.toml: the sources of the fileset readers live in directories of their own
-EXTRA_PACKAGE_DATA = {"sai_amd": ["csrc/plink/*.hip", "csrc/plink/*.hpp", "csrc/plink/*.cpp",
-                                  "csrc/eigenstrat/*.hip", "csrc/eigenstrat/*.hpp", "csrc/eigenstrat/*.cpp",
-                                  "csrc/pgen/*.hip", "csrc/pgen/*.hpp", "csrc/pgen/*.cpp",
-                                  "csrc/bcf/*.hip", "csrc/bcf/*.hpp", "csrc/bcf/*.cpp",
-                                  "csrc/packed_stats/*.hip", "csrc/packed_stats/*.hpp", "csrc/packed_stats/*.cpp"]}
+EXTRA_PACKAGE_DATA = {"sai_amd": [f"csrc/{d.name}/{pattern}" for d in sorted((ROOT / "sai_amd" / "csrc").iterdir()) if d.is_dir()
+                                  for pattern in ("*.hip", "*.hpp", "*.cpp")]}  # fmt: skip
 
 
 class WithExtraPackageData(setuptools.Distribution):
@@ -81,5 +77,6 @@ def metadata_for_old_setuptools() -> dict:
     )  # fmt: skip
 
 
-setup(cmdclass={"build_py": BuildWithLibrary, "develop": DevelopWithLibrary}, distclass=WithExtraPackageData,
-      **metadata_for_old_setuptools())  # fmt: skip
+if __name__ == "__main__":  # pip and setuptools run this file under that name; a test reads EXTRA_PACKAGE_DATA under another
+    setup(cmdclass={"build_py": BuildWithLibrary, "develop": DevelopWithLibrary}, distclass=WithExtraPackageData,
+          **metadata_for_old_setuptools())  # fmt: skip

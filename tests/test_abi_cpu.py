@@ -3,11 +3,11 @@ include/saihip.h declares, refuses to run without a device, and its host-side sy
 generator equals the numpy definition.  No GPU compute is attempted here."""
 
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
 
+import abi_checks
 from conftest import ROOT
 
 
@@ -21,16 +21,135 @@ def lib():
     return _ffi.load()
 
 
-def declared_functions():
-    text = (ROOT / "include" / "saihip.h").read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", text)))
+def families():
+    """(header, binding module) of saihip.h and of every family of entry points: the modules the build loads."""
+    from sai_amd._binding import family_modules
+
+    return [(abi_checks.header_of(module), module) for module in family_modules()]
+
+
+def test_every_header_has_one_binding_module_and_every_module_its_header():
+    headers = sorted(p.name for p in (ROOT / "include").iterdir())
+    assert sorted(header for header, _ in families()) == headers and len(headers) >= 10
+    from sai_amd import _build
+
+    assert sorted(p.name for p in _build.PUBLIC_HEADERS) == headers
+
+
+@pytest.mark.parametrize("header", sorted(p.name for p in (ROOT / "include").iterdir()))
+def test_header_binding_and_library_agree(lib, header):
+    (module,) = [m for h, m in families() if h == header]
+    names = abi_checks.declared_names(header)
+    assert names and names == sorted(module.SIGNATURES)
+    loaded = module.load()
+    for n in names:
+        assert hasattr(loaded, n), f"{n} is declared in {header} but not exported"
+    constant, value = abi_checks.version_constant(module)
+    (answer,) = [n for n in names if n.endswith("abi_version")]
+    assert answer == constant.lower() and abi_checks.header_macro(header, constant) == value == getattr(loaded, answer)()
+    assert set(module.HOST_SYMBOLS) <= set(module.SIGNATURES) and answer in module.HOST_SYMBOLS
+    assert module.load_host() is not None
+
+
+def test_a_library_without_a_family_or_of_another_version_is_refused(lib):
+    """The two refusals of ``_binding.extension``, on a handle that stands for a library built without the family."""
+    from sai_amd import _binding, _ffi_plink
+
+    class Without:
+        def __init__(self, missing=(), version=_ffi_plink.SAI_PLINK_ABI_VERSION):
+            self.missing, self.version = missing, version
+
+        def __getattr__(self, name):
+            if name.startswith("_") or name in self.missing:
+                raise AttributeError(name)
+            return type("Fn", (), {"__call__": lambda fn: self.version})()
+
+    real = _binding._ffi._lib
+    try:
+        _binding._ffi._lib = Without(missing=("sai_plink_decode",))
+        with pytest.raises(RuntimeError) as exc:
+            _ffi_plink.load()
+        assert str(exc.value) == ("sai_plink_decode is missing from libsaihip: the library was built without sai_amd/csrc/plink "
+                                  "(rebuild it: `python -c 'import __graft_entry__ as g; g.build()'`)")  # fmt: skip
+        _binding._ffi._lib = Without(version=7)
+        with pytest.raises(RuntimeError) as exc:
+            _ffi_plink.load()
+        assert str(exc.value) == "libsaihip: PLINK ABI 7 != expected 1"
+        _binding._ffi._lib = handle = Without()
+        assert _ffi_plink.load() is handle and handle._sai_attached_sai_plink_abi_version == tuple(_ffi_plink.SIGNATURES)
+    finally:
+        _binding._ffi._lib = real
+    assert _ffi_plink.load() is lib
+
+
+def test_staleness_inputs_are_the_list_the_build_used_to_spell_out():
+    """What an object is stale against, found by rule, is what sai_amd/_build.py listed by hand while it had ten
+    headers and six directories of .hpp files: those names, once, here."""
+    from sai_amd import _build
+
+    include, csrc = ROOT / "include", _build.CSRC
+    spelled_out = [include / "saihip.h", include / "saihip_plink.h", include / "saihip_eigenstrat.h", include / "saihip_pgen.h",
+                   include / "saihip_packed_ingest.h", include / "saihip_pgen_packed.h", include / "saihip_bcf.h", include / "saihip_bcf_device.h",
+                   include / "saihip_bcf_index.h", include / "saihip_packed_stats.h", *csrc.glob("*.hpp"), *csrc.glob("plink/*.hpp"),
+                   *csrc.glob("eigenstrat/*.hpp"), *csrc.glob("pgen/*.hpp"), *csrc.glob("bcf/*.hpp"), *csrc.glob("packed_stats/*.hpp")]  # fmt: skip
+    inputs = _build.staleness_inputs()
+    assert sorted(inputs) == sorted(spelled_out) and len(set(inputs)) == len(inputs) and all(p.is_file() for p in inputs)
+
+
+def test_units_exist_have_objects_of_their_own_and_their_directories_are_packaged():
+    from sai_amd import _build
+
+    assert all((_build.CSRC / u).is_file() for u in _build.UNITS) and set(_build.HOST_UNITS) < set(_build.UNITS)
+    assert _build.UNITS[-len(_build.HOST_UNITS):] == _build.HOST_UNITS and all(u.endswith(".cpp") for u in _build.HOST_UNITS)
+    assert sorted(str(p.relative_to(_build.CSRC)) for ext in ("hip", "cpp") for p in _build.CSRC.rglob(f"*.{ext}")) == sorted(_build.UNITS)
+    _build.check_object_names(_build.UNITS)
+    with pytest.raises(RuntimeError, match=r"^units with the same object name: bcf/core\.cpp core\.hip$"):
+        _build.check_object_names([*_build.UNITS, "bcf/core.cpp"])
+    patterns = abi_checks.package_data_patterns()
+    for unit in _build.UNITS:
+        directory, _, name = unit.rpartition("/")
+        assert not directory or f"csrc/{directory}/*{name[name.rindex('.'):]}" in patterns, unit
+    assert all(f"csrc/{p.parent.name}/*.hpp" in patterns for p in _build.CSRC.glob("*/*.hpp"))
+
+
+def test_compile_jobs_follow_max_jobs(monkeypatch):
+    import os
+
+    from sai_amd import _build
+
+    cpus = os.cpu_count() or 1
+    for value, want in (("1", 1), (str(cpus + 5), cpus), ("0", cpus), ("-3", cpus), ("many", cpus), ("", cpus)):
+        monkeypatch.setenv("MAX_JOBS", value)
+        assert _build._max_jobs() == want, value
+    monkeypatch.delenv("MAX_JOBS")
+    assert _build._max_jobs() == cpus
+
+
+def test_host_objects_are_compiled_once_per_kind(tmp_path, tmp_path_factory):
+    import os
+
+    import native_build
+
+    first = native_build.host_objects("san", tmp_path_factory)
+    from sai_amd import _build
+
+    assert len(first) == len(set(first)) == len(_build.HOST_UNITS)
+    stamps = [os.stat(o).st_mtime_ns for o in first]
+    assert native_build.host_objects("san", tmp_path_factory) == first and [os.stat(o).st_mtime_ns for o in first] == stamps
+    exe = native_build.dump_program("packed_freqs_dump", tmp_path_factory)["san"]
+    assert os.access(exe, os.X_OK) and [os.stat(o).st_mtime_ns for o in first] == stamps
+    # a refusal of the compiler fails the test with the compiler's words
+    bad = tmp_path / "bad.cpp"
+    bad.write_text("int main() { return no_such_name; }\n")
+    with pytest.raises(AssertionError, match="no_such_name"):
+        native_build.compile_object(bad, tmp_path / "bad.o", "san")
+    assert not (tmp_path / "bad.o").exists()
 
 
 def test_header_and_binding_agree(lib):
     from sai_amd import _ffi
 
-    names = declared_functions()
+    names = abi_checks.declared_names("saihip.h")
     assert len(names) >= 15
     assert sorted(_ffi.SIGNATURES) == names
     for n in names:

@@ -3,15 +3,15 @@ of GT vectors, against the VCF reader on the VCF text the file was written from.
 tests/bcf_builder.py (pure Python, from the format rules alone); the expectation always comes from the VCF readers,
 which the existing suites pin to the reference."""
 
-import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import abi_checks
 import bcf_builder as B
+import native_build
 from conftest import DATA, GOLDEN, ROOT
 
 # (name, chromosome, ancestral-allele file or None = one is written from the records)
@@ -256,20 +256,18 @@ def test_command_line_help_names_bcf():
 def test_header_binding_and_library_agree_and_the_other_headers_are_untouched():
     from sai_amd import _build, _ffi, _ffi_bcf, _ffi_pgen
 
-    strip = lambda name: re.sub(r"/\*.*?\*/", "", (ROOT / "include" / name).read_text(), flags=re.S)  # noqa: E731
-    text = strip("saihip_bcf.h")
-    names = sorted(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", text)))
+    names = abi_checks.declared_names("saihip_bcf.h")
     assert names == sorted(_ffi_bcf.SIGNATURES) and len(names) == 10
     lib = _ffi_bcf.load()
-    version = int(re.search(r"SAI_BCF_ABI_VERSION (\d+)", text).group(1))
+    version = abi_checks.header_macro("saihip_bcf.h", "SAI_BCF_ABI_VERSION")
     assert lib.sai_bcf_abi_version() == _ffi_bcf.SAI_BCF_ABI_VERSION == version == 1
     for name in ("SAI_BCF_STATUS_RANGE", "SAI_BCF_STATUS_BAD_VALUE", "SAI_BCF_STATUS_BAD_INDEX", "SAI_BCF_GT_ALIGN"):
-        assert int(re.search(rf"{name} (\d+)", text).group(1)) == getattr(_ffi_bcf, name)
+        assert abi_checks.header_macro("saihip_bcf.h", name) == getattr(_ffi_bcf, name)
     assert lib.sai_bcf_decode(None, None, 0, 0, None, None, None, None, 1, 1, None, -1, None, 2, None, 0, None, None) == _ffi.SAI_ERR_ARG
     assert b"ctx is NULL" in lib.sai_last_error()
     assert lib.sai_abi_version() == _ffi.SAI_ABI_VERSION == 16 and lib.sai_pgen_abi_version() == _ffi_pgen.SAI_PGEN_ABI_VERSION == 1
     assert "bcf/bcf_decode.hip" in _build.UNITS and "bcf/bcf_index.cpp" in _build.HOST_UNITS
-    assert '"saihip_bcf.h"' in (ROOT / "setup.py").read_text() and "csrc/bcf/*.hip" in (ROOT / "setup.py").read_text()
+    assert ROOT / "include" / "saihip_bcf.h" in _build.PUBLIC_HEADERS and "csrc/bcf/*.hip" in abi_checks.package_data_patterns()
 
 
 # ---- what is refused ------------------------------------------------------------------------------------
@@ -367,40 +365,12 @@ def test_what_is_refused(tmp_path):
 def dump_programs(tmp_path_factory):
     """tests/native/bcf_dump.cpp + the host units of libsaihip, once under ASan + UBSan with the runtimes linked in
     (as test_plink_cpu.py::dump_program builds its program) and once plain."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    import __graft_entry__ as entry
-
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.fail("g++ is needed to build the instrumented program")
-    out = tmp_path_factory.mktemp("bcf_dump")
-    sources = [entry.CSRC / u for u in entry.HOST_UNITS] + [ROOT / "tests" / "native" / "bcf_dump.cpp"]
-    kinds = {"san": [*entry.SAN_FLAGS, "-static-libasan", "-static-libubsan"], "plain": list(entry.HOST_FLAGS)}
-
-    def compile_one(job):
-        kind, src = job
-        obj = out / f"{kind}_{src.stem}.o"
-        res = subprocess.run([gxx, *kinds[kind], f"-I{ROOT / 'include'}", "-c", str(src), "-o", str(obj)], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-        return kind, str(obj)
-
-    with ThreadPoolExecutor(8) as pool:
-        objs = list(pool.map(compile_one, [(k, s) for k in kinds for s in sources]))
-    exes = {}
-    for kind, flags in kinds.items():
-        exes[kind] = str(out / f"bcf_dump_{kind}")
-        res = subprocess.run([gxx, *flags, *[o for k, o in objs if k == kind], "-o", exes[kind], "-lz", "-lpthread", "-ldl"], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-    return exes
+    return native_build.dump_program("bcf_dump", tmp_path_factory, kinds=("san", "plain"))
 
 
 def run_dump(exe, path, chrom, start, end, anc, request, cap=4096, n_threads=3):
-    env = dict(os.environ)
-    env.update(ASAN_OPTIONS="detect_leaks=1:exitcode=97:verify_asan_link_order=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=98")
-    cmd = [exe, path, chrom, str(-1 if start is None else start), str(-1 if end is None else end), anc or "-", str(n_threads), str(cap),
-           *[f"{s}:{p}" for s, p in request]]  # fmt: skip
-    return subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
+    return native_build.run_native(exe, [path, chrom, -1 if start is None else start, -1 if end is None else end, anc or "-", n_threads, cap,
+                                         *[f"{s}:{p}" for s, p in request]])  # fmt: skip
 
 
 def test_host_code_is_clean_under_asan_ubsan(tmp_path, dump_programs):

@@ -4,15 +4,15 @@ an index can be wrong, the knob, the header and its binding, and the stand-alone
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_checks
 import bcf_builder as B
 import csi_builder as X
 import csi_cases as K
+import native_build
 from conftest import GOLDEN, ROOT
 
 NONE, SEEK, WALK = 0, 1, 2
@@ -293,15 +293,13 @@ def test_every_way_an_index_can_be_wrong(tmp_path):
 def test_header_binding_and_library_agree_and_the_other_headers_are_untouched():
     from sai_amd import _build, _ffi, _ffi_bcf, _ffi_bcf_device, _ffi_bcf_index
 
-    strip = lambda name: re.sub(r"/\*.*?\*/", "", (ROOT / "include" / name).read_text(), flags=re.S)  # noqa: E731
-    text = strip("saihip_bcf_index.h")
-    names = sorted(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", text)))
+    names = abi_checks.declared_names("saihip_bcf_index.h")
     assert names == sorted(_ffi_bcf_index.SIGNATURES) and len(names) == 9
     lib = _ffi_bcf_index.load()
-    version = int(re.search(r"SAI_BCF_INDEX_ABI_VERSION (\d+)", text).group(1))
+    version = abi_checks.header_macro("saihip_bcf_index.h", "SAI_BCF_INDEX_ABI_VERSION")
     assert lib.sai_bcf_index_abi_version() == _ffi_bcf_index.SAI_BCF_INDEX_ABI_VERSION == version == 1
     for name in ("SAI_BCF_INDEX_NONE", "SAI_BCF_INDEX_SEEK", "SAI_BCF_INDEX_WALK"):
-        assert int(re.search(rf"{name} (\d+)", text).group(1)) == getattr(_ffi_bcf_index, name)
+        assert abi_checks.header_macro("saihip_bcf_index.h", name) == getattr(_ffi_bcf_index, name)
     assert set(_ffi_bcf_index.HOST_SYMBOLS) == set(_ffi_bcf_index.SIGNATURES)
     assert lib.sai_bcf_index_open(None, 0, None) == _ffi.SAI_ERR_ARG and b"NULL argument" in lib.sai_last_error()
     # the other headers keep their entry points and their version numbers
@@ -309,9 +307,9 @@ def test_header_binding_and_library_agree_and_the_other_headers_are_untouched():
     assert _ffi_bcf.load().sai_bcf_abi_version() == _ffi_bcf.SAI_BCF_ABI_VERSION == 1 and len(_ffi_bcf.SIGNATURES) == 10
     assert _ffi_bcf_device.load().sai_bcf_device_abi_version() == _ffi_bcf_device.SAI_BCF_DEVICE_ABI_VERSION == 1 and len(_ffi_bcf_device.SIGNATURES) == 13
     for header, module in (("saihip_bcf.h", _ffi_bcf), ("saihip_bcf_device.h", _ffi_bcf_device)):
-        assert sorted(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", strip(header)))) == sorted(module.SIGNATURES)
+        assert abi_checks.declared_names(header) == sorted(module.SIGNATURES)
     assert "bcf/csi_index.cpp" in _build.HOST_UNITS and "bcf/csi_index.cpp" in _build.UNITS
-    assert '"saihip_bcf_index.h"' in (ROOT / "setup.py").read_text() and "csrc/bcf/*.cpp" in (ROOT / "setup.py").read_text()
+    assert ROOT / "include" / "saihip_bcf_index.h" in _build.PUBLIC_HEADERS and "csrc/bcf/*.cpp" in abi_checks.package_data_patterns()
 
 
 def test_packed2_still_refuses_with_its_pinned_sentence(tmp_path, in_repo_root, monkeypatch):
@@ -334,37 +332,12 @@ def test_packed2_still_refuses_with_its_pinned_sentence(tmp_path, in_repo_root, 
 def dump_program(tmp_path_factory):
     """tests/native/csi_dump.cpp + the host units of libsaihip under ASan + UBSan with the runtimes linked in, as
     test_bcf_cpu.py::dump_programs builds its program."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    import __graft_entry__ as entry
-
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.fail("g++ is needed to build the instrumented program")
-    out = tmp_path_factory.mktemp("csi_dump")
-    sources = [entry.CSRC / u for u in entry.HOST_UNITS] + [ROOT / "tests" / "native" / "csi_dump.cpp"]
-    flags = [*entry.SAN_FLAGS, "-static-libasan", "-static-libubsan"]
-
-    def compile_one(src):
-        obj = out / f"{src.stem}.o"
-        res = subprocess.run([gxx, *flags, f"-I{ROOT / 'include'}", "-c", str(src), "-o", str(obj)], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-        return str(obj)
-
-    with ThreadPoolExecutor(8) as pool:
-        objs = list(pool.map(compile_one, sources))
-    exe = str(out / "csi_dump")
-    res = subprocess.run([gxx, *flags, *objs, "-o", exe, "-lz", "-lpthread", "-ldl"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
-    return exe
+    return native_build.dump_program("csi_dump", tmp_path_factory)["san"]
 
 
 def run_dump(exe, path, index, chrom, tid, regions, request, cap=4096, n_threads=3):
-    env = dict(os.environ)
-    env.update(ASAN_OPTIONS="detect_leaks=1:exitcode=97:verify_asan_link_order=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=98")
-    flat = [str(-1 if x is None else x) for reg in regions for x in reg]
-    cmd = [exe, path, index, chrom, str(tid), str(n_threads), str(cap), str(len(regions)), *flat, *[f"{s}:{p}" for s, p in request]]
-    return subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
+    flat = [-1 if x is None else x for reg in regions for x in reg]
+    return native_build.run_native(exe, [path, index, chrom, tid, n_threads, cap, len(regions), *flat, *[f"{s}:{p}" for s, p in request]])
 
 
 def test_the_stand_alone_program_under_the_sanitizers(tmp_path, dump_program):

@@ -5,15 +5,15 @@ runs the kernels against the twins on the same streams."""
 
 import ctypes as C
 import re
-import shutil
 import struct
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
+import abi_checks
 import bcf_builder as B
+import native_build
 from conftest import ROOT
 from test_bcf_cpu import FILES, REFUSED, _gt, anc_file, region_of, samples_of, small_bcf, vcf_text
 
@@ -400,42 +400,12 @@ def test_what_open_and_select_hand_to_the_host_route(tmp_path):
 def walk_dump_programs(tmp_path_factory):
     """tests/native/bcf_walk_dump.cpp + the host units of libsaihip, once under ASan + UBSan with the runtimes linked in
     (as test_bcf_cpu.py::dump_programs builds its program) and once plain."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    import __graft_entry__ as entry
-
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.fail("g++ is needed to build the instrumented program")
-    out = tmp_path_factory.mktemp("bcf_walk_dump")
-    sources = [entry.CSRC / u for u in entry.HOST_UNITS] + [ROOT / "tests" / "native" / "bcf_walk_dump.cpp"]
-    kinds = {"san": [*entry.SAN_FLAGS, "-static-libasan", "-static-libubsan"], "plain": list(entry.HOST_FLAGS)}
-
-    def compile_one(job):
-        kind, src = job
-        obj = out / f"{kind}_{src.stem}.o"
-        res = subprocess.run([gxx, *kinds[kind], f"-I{ROOT / 'include'}", "-c", str(src), "-o", str(obj)], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-        return kind, str(obj)
-
-    with ThreadPoolExecutor(8) as pool:
-        objs = list(pool.map(compile_one, [(k, s) for k in kinds for s in sources]))
-    exes = {}
-    for kind, flags in kinds.items():
-        exes[kind] = str(out / f"bcf_walk_dump_{kind}")
-        res = subprocess.run([gxx, *flags, *[o for k, o in objs if k == kind], "-o", exes[kind], "-lz", "-lpthread", "-ldl"], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-    return exes
+    return native_build.dump_program("bcf_walk_dump", tmp_path_factory, kinds=("san", "plain"))
 
 
 def run_walk_dump(exe, path, chrom, start, end, anc, seg_bytes, text_batch, whole_file, samples):
-    import os
-
-    env = dict(os.environ)
-    env.update(ASAN_OPTIONS="detect_leaks=1:exitcode=97:verify_asan_link_order=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=98")
-    cmd = [exe, str(path), chrom, str(-1 if start is None else start), str(-1 if end is None else end), anc or "-", str(seg_bytes), str(MAX_HEADS),
-           str(text_batch), str(int(whole_file)), *samples]  # fmt: skip
-    return subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
+    return native_build.run_native(exe, [path, chrom, -1 if start is None else start, -1 if end is None else end, anc or "-", seg_bytes, MAX_HEADS,
+                                         text_batch, int(whole_file), *samples])  # fmt: skip
 
 
 def test_host_code_is_clean_under_asan_ubsan(tmp_path, walk_dump_programs):
@@ -512,16 +482,17 @@ def test_host_code_is_clean_under_asan_ubsan(tmp_path, walk_dump_programs):
 def test_header_binding_and_library_agree():
     from sai_amd import _build, _ffi_bcf, _ffi_bcf_device as D
 
-    strip = lambda name: re.sub(r"/\*.*?\*/", "", (ROOT / "include" / name).read_text(), flags=re.S)  # noqa: E731
-    text = strip("saihip_bcf_device.h")
-    names = sorted(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", text)))
+    names = abi_checks.declared_names("saihip_bcf_device.h")
     assert names == sorted(D.SIGNATURES) and len(names) == 13
     lib = D.load()
-    version = int(re.search(r"SAI_BCF_DEVICE_ABI_VERSION (\d+)", text).group(1))
+    version = abi_checks.header_macro("saihip_bcf_device.h", "SAI_BCF_DEVICE_ABI_VERSION")
     assert lib.sai_bcf_device_abi_version() == D.SAI_BCF_DEVICE_ABI_VERSION == version == 1
-    for name in re.findall(r"#define (SAI_BCF_[A-Z_]+) \d+", text):
-        assert int(re.search(rf"{name} (\d+)", text).group(1)) == getattr(D, name), name
-    assert len(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", strip("saihip_bcf.h")))) == len(_ffi_bcf.SIGNATURES) == 10
+    macros = re.findall(r"#define (SAI_BCF_[A-Z_]+) \d+", abi_checks.header_text("saihip_bcf_device.h"))
+    assert len(macros) == 13
+    for name in macros:
+        assert abi_checks.header_macro("saihip_bcf_device.h", name) == getattr(D, name), name
+    assert len(abi_checks.declared_names("saihip_bcf.h")) == len(_ffi_bcf.SIGNATURES) == 10
     assert "bcf/bcf_walk.hip" in _build.UNITS and "bcf/bcf_feed.cpp" in _build.HOST_UNITS
-    assert '"saihip_bcf_device.h"' in (ROOT / "setup.py").read_text() and "csrc/bcf/*.hpp" in (ROOT / "setup.py").read_text()
+    assert ROOT / "include" / "saihip_bcf_device.h" in _build.PUBLIC_HEADERS and "csrc/bcf/*.hpp" in abi_checks.package_data_patterns()
+    assert _build.CSRC / "bcf" / "bcf_record.hpp" in _build.staleness_inputs()
     assert lib.sai_bcf_chain_segments(None, None, 0, 256, 8, None, 0, 0, None, None, None) != 0 and b"ctx is NULL" in lib.sai_last_error()

@@ -3,14 +3,11 @@ statement of the layout formula of saihip.h and of the table of saihip_packed_in
 (``plink.load_packed``) and what ``score(..., layout="packed2")`` refuses before it reads anything."""
 
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import abi_checks
+import native_build
 from conftest import ROOT
 from test_plink_cpu import HET, HOM_A1, HOM_A2, MISSING, sai_cli, small_fileset
 
@@ -207,22 +204,20 @@ def test_argument_errors_have_the_messages_of_the_int8_decoder():
 def test_header_binding_and_library_agree_and_the_plink_header_is_untouched():
     from sai_amd import _build, _ffi, _ffi_packed_ingest, _ffi_plink
 
-    strip = lambda name: re.sub(r"/\*.*?\*/", "", (ROOT / "include" / name).read_text(), flags=re.S)  # noqa: E731
-    text = strip("saihip_packed_ingest.h")
-    names = sorted(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", text)))
+    names = abi_checks.declared_names("saihip_packed_ingest.h")
     assert names == sorted(_ffi_packed_ingest.SIGNATURES) == ["sai_bed_pack2", "sai_bed_pack2_host", "sai_packed_ingest_abi_version"]
     assert not any(n.startswith("sai_plink_") for n in names)
     lib = _ffi_packed_ingest.load()
-    version = int(re.search(r"SAI_PACKED_INGEST_ABI_VERSION (\d+)", text).group(1))
+    version = abi_checks.header_macro("saihip_packed_ingest.h", "SAI_PACKED_INGEST_ABI_VERSION")
     assert lib.sai_packed_ingest_abi_version() == _ffi_packed_ingest.SAI_PACKED_INGEST_ABI_VERSION == version == 1
     assert lib.sai_bed_pack2(None, None, 0, 0, 0, None, None, 0, 1, None, -1, 2, None, 0, 0, None, None, None) == _ffi.SAI_ERR_ARG
     assert b"ctx is NULL" in lib.sai_last_error()
     # the PLINK header, its binding and the version numbers are as they were
-    plink_names = sorted(set(re.findall(r"\b(sai_plink_[a-z0-9_]+)\s*\(", strip("saihip_plink.h"))))
+    plink_names = abi_checks.declared_names("saihip_plink.h")
     assert plink_names == sorted(_ffi_plink.SIGNATURES) and len(plink_names) == 8
     assert lib.sai_abi_version() == _ffi.SAI_ABI_VERSION == 16 and lib.sai_plink_abi_version() == _ffi_plink.SAI_PLINK_ABI_VERSION == 1
     assert "plink/bed_pack2.hip" in _build.UNITS and "plink/bed_pack2_host.cpp" in _build.HOST_UNITS
-    assert '"saihip_packed_ingest.h"' in (ROOT / "setup.py").read_text()
+    assert ROOT / "include" / "saihip_packed_ingest.h" in _build.PUBLIC_HEADERS
 
 
 def anc_file(path, chrom, positions, alleles):
@@ -317,37 +312,13 @@ def test_command_line_lists_the_layout():
 @pytest.fixture(scope="module")
 def pack2_program(tmp_path_factory):
     """tests/native/bed_pack2_dump.cpp + the host units of libsaihip under ASan + UBSan, the runtimes linked in."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    import __graft_entry__ as entry
-
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.fail("g++ is needed to build the instrumented program")
-    out = tmp_path_factory.mktemp("bed_pack2_dump")
-    flags = [*entry.SAN_FLAGS, "-static-libasan", "-static-libubsan", f"-I{ROOT / 'include'}"]
-    sources = [entry.CSRC / u for u in entry.HOST_UNITS] + [ROOT / "tests" / "native" / "bed_pack2_dump.cpp"]
-
-    def compile_one(src):
-        obj = out / (src.stem + ".o")
-        res = subprocess.run([gxx, *flags, "-c", str(src), "-o", str(obj)], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-        return str(obj)
-
-    with ThreadPoolExecutor(min(8, len(sources))) as pool:
-        objs = list(pool.map(compile_one, sources))
-    exe = out / "bed_pack2_dump"
-    res = subprocess.run([gxx, *flags, *objs, "-o", str(exe), "-lz", "-lpthread", "-ldl"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
-    return str(exe)
+    return native_build.dump_program("bed_pack2_dump", tmp_path_factory)["san"]
 
 
 def test_host_decoder_is_clean_under_asan_ubsan(tmp_path, pack2_program):
     """The host decoder run (not only compiled) under the sanitizers as a program of its own, on rows in a file: the
     same block, status and unfit as the library, for runs, gathers, cut calls and indices out of range."""
     rng = np.random.default_rng(77)
-    env = dict(os.environ)
-    env.update(ASAN_OPTIONS="detect_leaks=1:exitcode=97:verify_asan_link_order=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=98")
     for n_ind, n_sites, first_col, ploidy, cut in [(1, 1, 0, 2, 0), (17, 65, 3, 1, 37), (65, 130, -1, 2, 64), (130, 63, 1, 2, 37), (64, 64, -1, 1, 0)]:
         n_cols = n_ind + 9
         row_bytes = (n_cols + 3) // 4
@@ -359,9 +330,8 @@ def test_host_decoder_is_clean_under_asan_ubsan(tmp_path, pack2_program):
         flip = rng.integers(0, 2, size=n_sites).astype(np.uint8)
         cols = np.arange(first_col, first_col + n_ind, dtype=np.int32) if first_col >= 0 else rng.integers(-1, n_cols + 1, size=n_ind).astype(np.int32)
         (tmp_path / "rows.bin").write_bytes(rows.tobytes())
-        cmd = [pack2_program, str(tmp_path / "rows.bin"), str(row_bytes), str(n_cols), str(ploidy), str(first_col), str(cut), "3",
-               ",".join(map(str, rib)), ",".join(map(str, flip)), ",".join(map(str, cols))]  # fmt: skip
-        res = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
+        res = native_build.run_native(pack2_program, [tmp_path / "rows.bin", row_bytes, n_cols, ploidy, first_col, cut, 3,
+                                                      ",".join(map(str, rib)), ",".join(map(str, flip)), ",".join(map(str, cols))])  # fmt: skip
         assert res.returncode == 0 and "runtime error" not in res.stderr and "Sanitizer" not in res.stderr, res.stderr[-3000:]
         lines = res.stdout.splitlines()
         fields, want_st, want_uf = expect(rows, row_bytes, rib, flip, n_cols, cols, ploidy)
@@ -370,5 +340,5 @@ def test_host_decoder_is_clean_under_asan_ubsan(tmp_path, pack2_program):
         packed = np.zeros(pack_numpy(fields).size, dtype=np.uint8)
         st, uf = pack_host(rows, row_bytes, rib, flip, n_cols, cols, first_col, ploidy, packed, n_sites, 0)
         assert st.tolist() == want_st.tolist() and uf.tolist() == want_uf.tolist() and packed.tobytes() == bytes.fromhex(lines[2])
-    res = subprocess.run([pack2_program, str(tmp_path / "rows.bin"), "2", "9", "2", "0", "0", "1", "0", "0", "0"], capture_output=True, text=True, env=env)
+    res = native_build.run_native(pack2_program, [tmp_path / "rows.bin", 2, 9, 2, 0, 0, 1, 0, 0, 0])
     assert res.returncode == 3 and "n_cols exceeds the 4 * row_bytes genotypes of a row" in res.stderr and "Sanitizer" not in res.stderr

@@ -5,13 +5,13 @@ file.  No EIGENSOFT program was at hand: the filesets are written here, from the
 DESIGN_INGEST.md ("EIGENSTRAT filesets"), never read from a fixture."""
 
 import os
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_checks
+import native_build
 from conftest import ROOT
 from test_plink_cpu import random_case, run_dump, sai_cli, vcf_expectation, write_vcf
 
@@ -428,19 +428,17 @@ def test_header_and_binding_agree():
     earlier headers and their versions are as they were."""
     from sai_amd import _ffi, _ffi_eigenstrat, _ffi_plink
 
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "saihip_eigenstrat.h").read_text(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(sai_eigenstrat_[a-z0-9_]+)\s*\(", text)))
-    assert names == sorted(_ffi_eigenstrat.SIGNATURES) and len(names) == 9
+    names = abi_checks.declared_names("saihip_eigenstrat.h")
+    assert names == sorted(_ffi_eigenstrat.SIGNATURES) and len(names) == 9 and all(n.startswith("sai_eigenstrat_") for n in names)
     lib = _ffi_eigenstrat.load()
-    version = int(re.search(r"SAI_EIGENSTRAT_ABI_VERSION (\d+)", text).group(1))
+    version = abi_checks.header_macro("saihip_eigenstrat.h", "SAI_EIGENSTRAT_ABI_VERSION")
     assert lib.sai_eigenstrat_abi_version() == _ffi_eigenstrat.SAI_EIGENSTRAT_ABI_VERSION == version == 1
     for name, value in (("STATUS_BAD_INDEX", _ffi_eigenstrat.SAI_EIGENSTRAT_STATUS_BAD_INDEX), ("STATUS_BAD_CHAR", _ffi_eigenstrat.SAI_EIGENSTRAT_STATUS_BAD_CHAR),
                         ("TEXT", _ffi_eigenstrat.TEXT), ("PACKED", _ffi_eigenstrat.PACKED), ("TRANSPOSED", _ffi_eigenstrat.TRANSPOSED)):  # fmt: skip
-        assert int(re.search(rf"SAI_EIGENSTRAT_{name} (\w+)", text).group(1), 0) == value
+        assert abi_checks.header_macro("saihip_eigenstrat.h", f"SAI_EIGENSTRAT_{name}") == value
     assert lib.sai_abi_version() == _ffi.SAI_ABI_VERSION == 16 and _ffi_plink.load().sai_plink_abi_version() == 1
     assert not any(n.startswith("sai_eigenstrat") for n in list(_ffi.SIGNATURES) + list(_ffi_plink.SIGNATURES))
-    plink_text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "saihip_plink.h").read_text(), flags=re.S)
-    assert len(set(re.findall(r"\b(sai_plink_[a-z0-9_]+)\s*\(", plink_text))) == 8 and "eigenstrat" not in plink_text
+    assert len(abi_checks.declared_names("saihip_plink.h")) == 8 and "eigenstrat" not in abi_checks.header_text("saihip_plink.h")
     assert "eigenstrat" not in (ROOT / "include" / "saihip.h").read_text().lower()
     assert lib.sai_eigenstrat_decode(None, 2, None, 0, 0, 0, None, None, 0, 1, None, -1, None, 0, None, 0, None, None) == _ffi.SAI_ERR_ARG
     assert b"ctx is NULL" in lib.sai_last_error()
@@ -451,29 +449,7 @@ def test_header_and_binding_agree():
 @pytest.fixture(scope="module")
 def dump_program(tmp_path_factory):
     """tests/native/eigenstrat_dump.cpp + the host units of libsaihip under ASan + UBSan, the runtimes linked in."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    import __graft_entry__ as entry
-
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.fail("g++ is needed to build the instrumented program")
-    out = tmp_path_factory.mktemp("eigenstrat_dump")
-    flags = [*entry.SAN_FLAGS, "-static-libasan", "-static-libubsan", f"-I{ROOT / 'include'}"]
-    sources = [entry.CSRC / u for u in entry.HOST_UNITS] + [ROOT / "tests" / "native" / "eigenstrat_dump.cpp"]
-
-    def compile_one(src):
-        obj = out / (src.stem + ".o")
-        res = subprocess.run([gxx, *flags, "-c", str(src), "-o", str(obj)], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-        return str(obj)
-
-    with ThreadPoolExecutor(min(8, len(sources))) as pool:
-        objs = list(pool.map(compile_one, sources))
-    exe = out / "eigenstrat_dump"
-    res = subprocess.run([gxx, *flags, *objs, "-o", str(exe), "-lz", "-lpthread", "-ldl"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
-    return str(exe)
+    return native_build.dump_program("eigenstrat_dump", tmp_path_factory)["san"]
 
 
 def test_host_code_is_clean_under_asan_ubsan(tmp_path, dump_program):

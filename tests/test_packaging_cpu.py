@@ -64,6 +64,13 @@ def test_install_builds_the_library_and_the_sai_command_prints_the_reference_fla
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
     assert (target / "sai_amd" / "lib" / "libsaihip.so").exists() and (target / "sai_amd" / "include" / "saihip.h").exists()
     assert (target / "sai_amd" / "csrc" / "windows.hip").exists() and (target / "sai" / "__init__.py").exists()
+    # every public header and every source the library is built from travel with the package: it can rebuild itself
+    headers = sorted(p.name for p in (ROOT / "include").iterdir())
+    assert len(headers) >= 10 and sorted(p.name for p in (target / "sai_amd" / "include").iterdir()) == headers
+    csrc = ROOT / "sai_amd" / "csrc"
+    sources = sorted(str(p.relative_to(csrc)) for ext in ("hip", "hpp", "cpp") for p in csrc.rglob(f"*.{ext}"))
+    assert len(sources) >= 59 and "pgen/pgen_codes.hpp" in sources
+    assert [s for s in sources if not (target / "sai_amd" / "csrc" / s).is_file()] == []
     script = target / "bin" / "sai"
     assert script.exists()
     env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}

@@ -4,14 +4,11 @@ statement of include/saihip_packed_stats.h, its argument errors, the header / bi
 tests/test_packed_stats_device.py runs the kernel against the twin on the same shapes."""
 
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import abi_checks
+import native_build
 from conftest import ROOT
 from test_bed_pack2_cpu import pack_numpy
 from test_plink_cpu import fileset_from_vcf
@@ -162,14 +159,12 @@ def test_header_binding_and_library_agree_and_the_other_headers_are_untouched():
     from sai_amd import (_build, _ffi, _ffi_bcf, _ffi_bcf_device, _ffi_eigenstrat, _ffi_packed_ingest, _ffi_packed_stats, _ffi_pgen,
                          _ffi_pgen_packed, _ffi_plink)  # fmt: skip
 
-    strip = lambda name: re.sub(r"/\*.*?\*/", "", (ROOT / "include" / name).read_text(), flags=re.S)  # noqa: E731
-    text = strip("saihip_packed_stats.h")
-    names = sorted(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", text)))
+    names = abi_checks.declared_names("saihip_packed_stats.h")
     assert names == sorted(_ffi_packed_stats.SIGNATURES) == ["sai_packed2_site_freqs", "sai_packed2_site_freqs_host", "sai_packed_stats_abi_version"]
     lib = _ffi_packed_stats.load()
-    version = int(re.search(r"SAI_PACKED_STATS_ABI_VERSION (\d+)", text).group(1))
+    version = abi_checks.header_macro("saihip_packed_stats.h", "SAI_PACKED_STATS_ABI_VERSION")
     assert lib.sai_packed_stats_abi_version() == _ffi_packed_stats.SAI_PACKED_STATS_ABI_VERSION == version == 1
-    n_pops = int(re.search(r"SAI_PACKED_FREQ_POPS (\d+)", text).group(1))
+    n_pops = abi_checks.header_macro("saihip_packed_stats.h", "SAI_PACKED_FREQ_POPS")
     assert n_pops == _ffi_packed_stats.SAI_PACKED_FREQ_POPS == 2 + _ffi.SAI_FUSED_SRC + 1 == 9
     assert set(_ffi_packed_stats.HOST_SYMBOLS) == {"sai_packed_stats_abi_version", "sai_packed2_site_freqs_host"}
     assert lib.sai_packed2_site_freqs(None, 1, 1, None, None, None) == _ffi.SAI_ERR_ARG and b"ctx is NULL" in lib.sai_last_error()
@@ -184,8 +179,8 @@ def test_header_binding_and_library_agree_and_the_other_headers_are_untouched():
                                  (_ffi_bcf_device, "sai_bcf_device_abi_version", "SAI_BCF_DEVICE_ABI_VERSION")]:  # fmt: skip
         assert getattr(module.load(), fn)() == getattr(module, constant) == 1, fn
     assert "packed_stats/packed2_freqs.hip" in _build.UNITS and "packed_stats/packed2_freqs_host.cpp" in _build.HOST_UNITS
-    setup = (ROOT / "setup.py").read_text()
-    assert '"saihip_packed_stats.h"' in setup and "csrc/packed_stats/*.hpp" in setup
+    assert ROOT / "include" / "saihip_packed_stats.h" in _build.PUBLIC_HEADERS and "csrc/packed_stats/*.hpp" in abi_checks.package_data_patterns()
+    assert _build.CSRC / "packed_stats" / "packed2_freqs_args.hpp" in _build.staleness_inputs()
 
 
 def test_the_abba_baba_family_is_admitted_and_dd_is_not(tmp_path, in_repo_root, monkeypatch):
@@ -231,35 +226,22 @@ def test_command_line_names_the_statistics_of_the_layout():
 
 @pytest.fixture(scope="module")
 def freqs_program(tmp_path_factory):
-    """tests/native/packed_freqs_dump.cpp + packed_stats/packed2_freqs_host.cpp (and host_core.cpp, which holds the
-    error text) under ASan + UBSan, the runtimes linked in."""
-    import __graft_entry__ as entry
-
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.fail("g++ is needed to build the instrumented program")
-    out = tmp_path_factory.mktemp("packed_freqs_dump")
-    flags = [*entry.SAN_FLAGS, "-static-libasan", "-static-libubsan", f"-I{ROOT / 'include'}"]
-    sources = [entry.CSRC / "packed_stats" / "packed2_freqs_host.cpp", entry.CSRC / "host_core.cpp", ROOT / "tests" / "native" / "packed_freqs_dump.cpp"]
-    exe = out / "packed_freqs_dump"
-    res = subprocess.run([gxx, *flags, *map(str, sources), "-o", str(exe), "-lpthread", "-ldl"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
-    return str(exe)
+    """tests/native/packed_freqs_dump.cpp + the host units of libsaihip (packed_stats/packed2_freqs_host.cpp among
+    them) under ASan + UBSan, the runtimes linked in."""
+    return native_build.dump_program("packed_freqs_dump", tmp_path_factory)["san"]
 
 
 def test_host_twin_is_clean_under_asan_ubsan(tmp_path, freqs_program):
     """The host twin run (not only compiled) under the sanitizers as a program of its own, on blocks of exactly the size
     the header asks for: the doubles of the numpy statement and of the library."""
     rng = np.random.default_rng(78)
-    env = dict(os.environ)
-    env.update(ASAN_OPTIONS="detect_leaks=1:exitcode=97:verify_asan_link_order=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=98")
 
     def run(n_sites, n_threads, n_inds, ploidies, blocks):
         args = []
         for p, (n_ind, ploidy, block) in enumerate(zip(n_inds, ploidies, blocks)):
             (tmp_path / f"b{p}.bin").write_bytes(block.tobytes())
             args.append(f"{n_ind}:{ploidy}:{tmp_path / f'b{p}.bin'}")
-        return subprocess.run([freqs_program, str(n_sites), str(n_threads), *args], capture_output=True, text=True, env=env, timeout=300)
+        return native_build.run_native(freqs_program, [n_sites, n_threads, *args])
 
     for n_sites in N_SITES:
         for n_inds in ([n for n in N_IND[:9]], N_IND[9:]):

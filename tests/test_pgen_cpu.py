@@ -4,13 +4,13 @@ written from the rules alone); the expectation comes from the code matrix throug
 from the PLINK 1 route on the same genotypes, or from the worked example committed as hex."""
 
 import os
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_checks
+import native_build
 import pgen_builder as B
 from conftest import ROOT
 from test_pgen_builder_cpu import EXAMPLE_CODES, EXAMPLE_TYPES, example_bytes
@@ -542,20 +542,18 @@ def test_header_and_binding_agree():
     headers and their versions are as they were."""
     from sai_amd import _ffi, _ffi_eigenstrat, _ffi_pgen, _ffi_plink
 
-    strip = lambda name: re.sub(r"/\*.*?\*/", "", (ROOT / "include" / name).read_text(), flags=re.S)  # noqa: E731
-    text = strip("saihip_pgen.h")
-    names = sorted(set(re.findall(r"\b(sai_pgen_[a-z0-9_]+)\s*\(", text)))
-    assert names == sorted(_ffi_pgen.SIGNATURES) and len(names) == 8
+    names = abi_checks.declared_names("saihip_pgen.h")
+    assert names == sorted(_ffi_pgen.SIGNATURES) and len(names) == 8 and all(n.startswith("sai_pgen_") for n in names)
     lib = _ffi_pgen.load()
-    version = int(re.search(r"SAI_PGEN_ABI_VERSION (\d+)", text).group(1))
+    version = abi_checks.header_macro("saihip_pgen.h", "SAI_PGEN_ABI_VERSION")
     assert lib.sai_pgen_abi_version() == _ffi_pgen.SAI_PGEN_ABI_VERSION == version == 1
-    assert int(re.search(r"SAI_PGEN_STATUS_BAD_INDEX (\w+)", text).group(1), 0) == _ffi_pgen.SAI_PGEN_STATUS_BAD_INDEX == BAD_INDEX
-    assert int(re.search(r"SAI_PGEN_STATUS_BAD_RECORD (\w+)", text).group(1), 0) == _ffi_pgen.SAI_PGEN_STATUS_BAD_RECORD == BAD_RECORD
+    assert abi_checks.header_macro("saihip_pgen.h", "SAI_PGEN_STATUS_BAD_INDEX") == _ffi_pgen.SAI_PGEN_STATUS_BAD_INDEX == BAD_INDEX
+    assert abi_checks.header_macro("saihip_pgen.h", "SAI_PGEN_STATUS_BAD_RECORD") == _ffi_pgen.SAI_PGEN_STATUS_BAD_RECORD == BAD_RECORD
     # the earlier headers: versions, the number of their entry points, and no name of theirs is new
     assert lib.sai_abi_version() == _ffi.SAI_ABI_VERSION == 16
     assert _ffi_plink.load().sai_plink_abi_version() == 1 and _ffi_eigenstrat.load().sai_eigenstrat_abi_version() == 1
-    assert len(set(re.findall(r"\b(sai_plink_[a-z0-9_]+)\s*\(", strip("saihip_plink.h")))) == 8 == len(_ffi_plink.SIGNATURES)
-    assert len(set(re.findall(r"\b(sai_eigenstrat_[a-z0-9_]+)\s*\(", strip("saihip_eigenstrat.h")))) == 9 == len(_ffi_eigenstrat.SIGNATURES)
+    assert len(abi_checks.declared_names("saihip_plink.h")) == 8 == len(_ffi_plink.SIGNATURES)
+    assert len(abi_checks.declared_names("saihip_eigenstrat.h")) == 9 == len(_ffi_eigenstrat.SIGNATURES)
     for other in ("saihip.h", "saihip_plink.h", "saihip_eigenstrat.h"):
         assert "pgen" not in (ROOT / "include" / other).read_text().lower()
     assert not any(n.startswith("sai_pgen") for n in [*_ffi.SIGNATURES, *_ffi_plink.SIGNATURES, *_ffi_eigenstrat.SIGNATURES])
@@ -571,9 +569,9 @@ def test_packaging_and_build_lists():
     from sai_amd import _build
 
     assert "pgen/pgen_decode.hip" in _build.UNITS and "pgen/pgen_index.cpp" in _build.UNITS
-    setup_text = (ROOT / "setup.py").read_text()
-    assert all(f'"csrc/pgen/*.{ext}"' in setup_text for ext in ("hip", "hpp", "cpp")) and '"saihip_pgen.h"' in setup_text
-    assert 'CSRC.glob("pgen/*.hpp")' in (ROOT / "sai_amd" / "_build.py").read_text()
+    assert {f"csrc/pgen/*.{ext}" for ext in ("hip", "hpp", "cpp")} <= set(abi_checks.package_data_patterns())
+    assert ROOT / "include" / "saihip_pgen.h" in _build.PUBLIC_HEADERS
+    assert {_build.CSRC / "pgen" / "pgen_codes.hpp", ROOT / "include" / "saihip_pgen.h"} <= set(_build.staleness_inputs())
 
 
 # ---- corrupted records ----
@@ -701,29 +699,7 @@ def test_corrupted_records_are_flagged_and_zeroed():
 @pytest.fixture(scope="module")
 def dump_program(tmp_path_factory):
     """tests/native/pgen_dump.cpp + the host units of libsaihip under ASan + UBSan, the runtimes linked in."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    import __graft_entry__ as entry
-
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.fail("g++ is needed to build the instrumented program")
-    out = tmp_path_factory.mktemp("pgen_dump")
-    flags = [*entry.SAN_FLAGS, "-static-libasan", "-static-libubsan", f"-I{ROOT / 'include'}"]
-    sources = [entry.CSRC / u for u in entry.HOST_UNITS] + [ROOT / "tests" / "native" / "pgen_dump.cpp"]
-
-    def compile_one(src):
-        obj = out / (src.stem + ".o")
-        res = subprocess.run([gxx, *flags, "-c", str(src), "-o", str(obj)], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-        return str(obj)
-
-    with ThreadPoolExecutor(min(8, len(sources))) as pool:
-        objs = list(pool.map(compile_one, sources))
-    exe = out / "pgen_dump"
-    res = subprocess.run([gxx, *flags, *objs, "-o", str(exe), "-lz", "-lpthread", "-ldl"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
-    return str(exe)
+    return native_build.dump_program("pgen_dump", tmp_path_factory)["san"]
 
 
 def test_host_code_is_clean_under_asan_ubsan(tmp_path, dump_program):
@@ -756,9 +732,7 @@ def test_host_code_is_clean_under_asan_ubsan(tmp_path, dump_program):
     flips = np.arange(len(rec)) % 2
     (tmp_path / "records.bin").write_bytes(data)
     (tmp_path / "records.txt").write_text("".join(" ".join(str(int(v)) for v in [*rec[r], *base[r], flips[r]]) + "\n" for r in range(len(rec))))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:exitcode=97:verify_asan_link_order=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=98")
-    res = subprocess.run([dump_program, "--records", str(tmp_path / "records.bin"), str(tmp_path / "records.txt"), str(n)], capture_output=True,
-                         text=True, env=env, timeout=300)  # fmt: skip
+    res = native_build.run_native(dump_program, ["--records", tmp_path / "records.bin", tmp_path / "records.txt", n])
     assert res.returncode == 0 and "runtime error" not in res.stderr and "Sanitizer" not in res.stderr, res.stderr[-3000:]
     table = np.array([[int(v) for v in ln.split()] for ln in res.stdout.splitlines()], dtype=np.int64)
     check_corrupted(table[:, 1:].astype(np.int8), table[:, 0], codes, what, list(range(n)), [2] * n, flips.astype(np.uint8))

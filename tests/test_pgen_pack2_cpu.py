@@ -5,12 +5,12 @@ numpy statement of the layout formula of saihip.h and of the table of saihip_pge
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_checks
+import native_build
 import pgen_builder as B
 from conftest import ROOT
 from test_bed_pack2_cpu import pack_numpy, site_words, tile_words
@@ -216,21 +216,19 @@ def test_argument_errors():
 def test_header_binding_and_library_agree_and_the_other_headers_are_untouched():
     from sai_amd import _build, _ffi, _ffi_packed_ingest, _ffi_pgen, _ffi_pgen_packed
 
-    strip = lambda name: re.sub(r"/\*.*?\*/", "", (ROOT / "include" / name).read_text(), flags=re.S)  # noqa: E731
-    text = strip("saihip_pgen_packed.h")
-    names = sorted(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", text)))
+    names = abi_checks.declared_names("saihip_pgen_packed.h")
     assert names == sorted(_ffi_pgen_packed.SIGNATURES) == ["sai_pgen_pack2", "sai_pgen_pack2_host", "sai_pgen_packed_abi_version"]
     lib = _ffi_pgen_packed.load()
-    version = int(re.search(r"SAI_PGEN_PACKED_ABI_VERSION (\d+)", text).group(1))
+    version = abi_checks.header_macro("saihip_pgen_packed.h", "SAI_PGEN_PACKED_ABI_VERSION")
     assert lib.sai_pgen_packed_abi_version() == _ffi_pgen_packed.SAI_PGEN_PACKED_ABI_VERSION == version == 1
     assert lib.sai_pgen_pack2(None, None, 0, 0, None, None, None, 1, 1, None, -1, 2, None, 0, 0, None, None, None) == _ffi.SAI_ERR_ARG
     assert b"ctx is NULL" in lib.sai_last_error()
     # the headers beside it, their bindings and the version numbers are as they were
-    assert len(set(re.findall(r"\b(sai_pgen_[a-z0-9_]+)\s*\(", strip("saihip_pgen.h")))) == len(_ffi_pgen.SIGNATURES) == 8
-    assert len(set(re.findall(r"\b(sai_[a-z0-9_]+)\s*\(", strip("saihip_packed_ingest.h")))) == len(_ffi_packed_ingest.SIGNATURES) == 3
+    assert len(abi_checks.declared_names("saihip_pgen.h")) == len(_ffi_pgen.SIGNATURES) == 8
+    assert len(abi_checks.declared_names("saihip_packed_ingest.h")) == len(_ffi_packed_ingest.SIGNATURES) == 3
     assert lib.sai_abi_version() == _ffi.SAI_ABI_VERSION == 16 and lib.sai_pgen_abi_version() == 1 and lib.sai_packed_ingest_abi_version() == 1
     assert "pgen/pgen_pack2.hip" in _build.UNITS and "pgen/pgen_pack2_host.cpp" in _build.HOST_UNITS
-    assert '"saihip_pgen_packed.h"' in (ROOT / "setup.py").read_text()
+    assert ROOT / "include" / "saihip_pgen_packed.h" in _build.PUBLIC_HEADERS
 
 
 def anc_file(path, chrom, positions, alleles):
@@ -406,38 +404,16 @@ def test_command_line_names_the_pfile_in_the_layout_help():
 @pytest.fixture(scope="module")
 def pack2_program(tmp_path_factory):
     """tests/native/pgen_pack2_dump.cpp + the host units of libsaihip under ASan + UBSan, the runtimes linked in."""
-    from concurrent.futures import ThreadPoolExecutor
-
     import __graft_entry__ as entry
 
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.fail("g++ is needed to build the instrumented program")
-    out = tmp_path_factory.mktemp("pgen_pack2_dump")
-    flags = [*entry.SAN_FLAGS, "-static-libasan", "-static-libubsan", f"-I{ROOT / 'include'}"]
-    sources = [entry.CSRC / u for u in entry.HOST_UNITS] + [ROOT / "tests" / "native" / "pgen_pack2_dump.cpp"]
-    assert entry.CSRC / "pgen" / "pgen_pack2_host.cpp" in sources
-
-    def compile_one(src):
-        obj = out / (src.stem + ".o")
-        res = subprocess.run([gxx, *flags, "-c", str(src), "-o", str(obj)], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-        return str(obj)
-
-    with ThreadPoolExecutor(min(8, len(sources))) as pool:
-        objs = list(pool.map(compile_one, sources))
-    exe = out / "pgen_pack2_dump"
-    res = subprocess.run([gxx, *flags, *objs, "-o", str(exe), "-lz", "-lpthread", "-ldl"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
-    return str(exe)
+    assert "pgen/pgen_pack2_host.cpp" in entry.HOST_UNITS
+    return native_build.dump_program("pgen_pack2_dump", tmp_path_factory)["san"]
 
 
 def test_host_decoder_is_clean_under_asan_ubsan(tmp_path, pack2_program):
     """The host decoder run (not only compiled) under the sanitizers as a program of its own: the worked example and
     the batch of damaged records, read from a heap block of exactly the batch's size -- the same block, status and
     unfit as the numpy statement and as the library."""
-    env = dict(os.environ)
-    env.update(ASAN_OPTIONS="detect_leaks=1:exitcode=97:verify_asan_link_order=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=98")
     example, table = B.build_pgen(EXAMPLE_CODES, EXAMPLE_TYPES)
     ex_rec, ex_base = tables_of(table)
     n = 300
@@ -451,9 +427,8 @@ def test_host_decoder_is_clean_under_asan_ubsan(tmp_path, pack2_program):
         flip = (np.arange(len(rec_)) % 2).astype(np.uint8)
         (tmp_path / "bytes.bin").write_bytes(bytes(data))
         (tmp_path / "records.txt").write_text("".join(" ".join(str(int(v)) for v in [*rec_[r], *base_[r], flip[r]]) + "\n" for r in range(len(rec_))))
-        cmd = [pack2_program, str(tmp_path / "bytes.bin"), str(tmp_path / "records.txt"), str(sample_ct), str(ploidy), str(first_col), str(cut),
-               "3", ",".join(map(str, cols))]  # fmt: skip
-        res = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
+        res = native_build.run_native(pack2_program, [tmp_path / "bytes.bin", tmp_path / "records.txt", sample_ct, ploidy, first_col, cut, 3,
+                                                      ",".join(map(str, cols))])  # fmt: skip
         assert res.returncode == 0 and "runtime error" not in res.stderr and "Sanitizer" not in res.stderr, res.stderr[-3000:]
         lines = res.stdout.splitlines()
         fields, want_st, want_uf = expect(codes_, flip, cols, ploidy)
@@ -463,6 +438,5 @@ def test_host_decoder_is_clean_under_asan_ubsan(tmp_path, pack2_program):
         st, uf = pack_host(data, rec_, base_, flip, sample_ct, cols, first_col, ploidy, packed, len(rec_), 0)
         assert st.tolist() == want_st.tolist() and uf.tolist() == want_uf.tolist() and packed.tobytes() == bytes.fromhex(lines[2])
         assert (want_st == BAD_RECORD).any() == (data is damaged)
-    res = subprocess.run([pack2_program, str(tmp_path / "bytes.bin"), str(tmp_path / "records.txt"), "300", "2", "299", "0", "1", "0,1"],
-                         capture_output=True, text=True, env=env)  # fmt: skip
+    res = native_build.run_native(pack2_program, [tmp_path / "bytes.bin", tmp_path / "records.txt", 300, 2, 299, 0, 1, "0,1"])
     assert res.returncode == 3 and "first_col + n_slots exceeds sample_ct" in res.stderr and "Sanitizer" not in res.stderr

@@ -5,13 +5,14 @@ the filesets are written here, by a converter of a dozen lines, never read from 
 
 import gzip
 import os
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import abi_checks
+import native_build
 from conftest import ROOT
 
 # PLINK 1 codes (bits 1:0 of a sample's pair): 0 = A1 A1, 1 = missing, 2 = heterozygous, 3 = A2 A2
@@ -238,37 +239,12 @@ def test_host_decode_equals_the_vcf_loader_on_random_matrices(tmp_path, seed):
 @pytest.fixture(scope="module")
 def dump_program(tmp_path_factory):
     """tests/native/plink_dump.cpp + the host units of libsaihip under ASan + UBSan, the runtimes linked in."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    import __graft_entry__ as entry
-
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.fail("g++ is needed to build the instrumented program")
-    out = tmp_path_factory.mktemp("plink_dump")
-    flags = [*entry.SAN_FLAGS, "-static-libasan", "-static-libubsan", f"-I{ROOT / 'include'}"]
-    sources = [entry.CSRC / u for u in entry.HOST_UNITS] + [ROOT / "tests" / "native" / "plink_dump.cpp"]
-
-    def compile_one(src):
-        obj = out / (src.stem + ".o")
-        res = subprocess.run([gxx, *flags, "-c", str(src), "-o", str(obj)], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-        return str(obj)
-
-    with ThreadPoolExecutor(min(8, len(sources))) as pool:
-        objs = list(pool.map(compile_one, sources))
-    exe = out / "plink_dump"
-    res = subprocess.run([gxx, *flags, *objs, "-o", str(exe), "-lz", "-lpthread", "-ldl"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
-    return str(exe)
+    return native_build.dump_program("plink_dump", tmp_path_factory)["san"]
 
 
 def run_dump(exe, prefix, chrom, start, end, anc, request, n_threads=3):
-    env = dict(os.environ)
-    env.update(ASAN_OPTIONS="detect_leaks=1:exitcode=97:verify_asan_link_order=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=98")
-    cmd = [exe, prefix, chrom, str(-1 if start is None else start), str(-1 if end is None else end), anc or "-", str(n_threads),
-           *[f"{s}:{p}" for s, p in request]]  # fmt: skip
-    return subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
+    return native_build.run_native(exe, [prefix, chrom, -1 if start is None else start, -1 if end is None else end, anc or "-", n_threads,
+                                         *[f"{s}:{p}" for s, p in request]])  # fmt: skip
 
 
 def test_host_code_is_clean_under_asan_ubsan(tmp_path, dump_program):
@@ -432,15 +408,12 @@ def test_command_line(tmp_path):
 def test_header_and_binding_agree():
     """include/saihip_plink.h, sai_amd/_ffi_plink.py and the library name the same entry points; the first header
     and its version are as they were."""
-    import re
-
     from sai_amd import _ffi, _ffi_plink
 
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "saihip_plink.h").read_text(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(sai_plink_[a-z0-9_]+)\s*\(", text)))
-    assert names == sorted(_ffi_plink.SIGNATURES) and len(names) == 8
+    names = abi_checks.declared_names("saihip_plink.h")
+    assert names == sorted(_ffi_plink.SIGNATURES) and len(names) == 8 and all(n.startswith("sai_plink_") for n in names)
     lib = _ffi_plink.load()
-    assert lib.sai_plink_abi_version() == _ffi_plink.SAI_PLINK_ABI_VERSION == int(re.search(r"SAI_PLINK_ABI_VERSION (\d+)", text).group(1))
+    assert lib.sai_plink_abi_version() == _ffi_plink.SAI_PLINK_ABI_VERSION == abi_checks.header_macro("saihip_plink.h", "SAI_PLINK_ABI_VERSION")
     assert lib.sai_abi_version() == _ffi.SAI_ABI_VERSION == 16 and not any(n.startswith("sai_plink") for n in _ffi.SIGNATURES)
     assert lib.sai_plink_decode(None, None, 0, 0, 0, None, None, 0, 1, None, -1, None, 0, None, 0, None, None) == _ffi.SAI_ERR_ARG
     assert b"ctx is NULL" in lib.sai_last_error()
