@@ -10,10 +10,11 @@ from typing import Optional, Sequence
 
 import sai_amd.stats  # noqa: F401  (fills STAT_REGISTRY)
 from sai_amd import __version__
+from sai_amd.parsers.convert_parser import add_convert_parser
 from sai_amd.parsers.outlier_parser import add_outlier_parser
 from sai_amd.parsers.score_parser import add_score_parser
 
-_COMMANDS = (add_score_parser, add_outlier_parser)
+_COMMANDS = (add_score_parser, add_outlier_parser, add_convert_parser)
 
 
 def _set_sigpipe_handler() -> None:

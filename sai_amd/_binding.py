@@ -1,5 +1,7 @@
 """What every ``_ffi_X`` module does with its table: declare the prototypes of one family of entry points on the
-handle ``_ffi`` returns, refuse a library that lacks one of them or answers another version number.
+handle ``_ffi`` returns, refuse a library that lacks one of them or answers another version number.  A group of entry
+points that is internal to the package (declared in a ``.hpp`` under sai_amd/csrc, bound by the one module that calls
+them: ``utils/bed_writer.py``) uses ``extension`` the same way, without being a family: it is not in ``family_modules``.
 
 A family is a header of its own under include/ (``saihip_X.h``) with its own version number, bound by
 ``sai_amd/_ffi_X.py``: constants, ``SIGNATURES``, ``HOST_SYMBOLS``, and one call of ``extension``.  ``_ffi``
@@ -25,8 +27,9 @@ def family_modules() -> list:
 
 
 def extension(tag: str, header: str, version_symbol: str, version: int, signatures: dict, host_symbols, built_from: str):
-    """``(load, load_host)`` of one family.  ``tag`` names it in the version message ("PLINK"), ``header`` is its
-    file under include/, ``version_symbol`` the entry point that answers ``version``, ``built_from`` the sources
+    """``(load, load_host)`` of one family or internal group.  ``tag`` names it in the version message ("PLINK"), ``header``
+    is the file that declares it, as the docstrings name it (a family's file under include/; a path from the repository
+    root for an internal group), ``version_symbol`` the entry point that answers ``version``, ``built_from`` the sources
     under sai_amd/csrc a library without these entry points was built without."""
     memo = "_sai_attached_" + version_symbol
 

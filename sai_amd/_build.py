@@ -28,6 +28,8 @@ HOST_UNITS = [
     "text_out.cpp",
     "plink/plink_index.cpp",
     "plink/bed_pack2_host.cpp",
+    "plink/bed_encode_host.cpp",
+    "plink/vcf_sites.cpp",
     "eigenstrat/eigenstrat_index.cpp",
     "pgen/pgen_index.cpp",
     "pgen/pgen_pack2_host.cpp",
@@ -52,6 +54,7 @@ UNITS = [
     "lines.hip",
     "plink/bed_decode.hip",
     "plink/bed_pack2.hip",
+    "plink/bed_encode.hip",
     "eigenstrat/geno_decode.hip",
     "eigenstrat/geno_transpose.hip",
     "pgen/pgen_decode.hip",
@@ -195,3 +198,6 @@ def build(force: bool = False, sanitize: bool = False) -> None:
 
     for module in family_modules():  # every symbol of include/saihip.h and of each include/saihip_X.h resolves
         module.load()
+    from sai_amd.utils import bed_writer  # ... and the converter's, declared in csrc/plink/bed_export.hpp and bound where they are used
+
+    bed_writer.load()

@@ -1,0 +1,59 @@
+"""``sai convert`` sub-command: a VCF's calls written as a PLINK 1 fileset.  Not a command of the reference."""
+
+from __future__ import annotations
+
+import argparse
+import json
+
+from ..sai import convert
+from .argument_validation import existed_file, positive_int
+
+PROMISE = ("Reading the fileset at the ploidies it was written with gives the block the VCF reader gives, byte for byte, "
+           "so `sai score` on it writes the same files as on the VCF.")  # fmt: skip
+
+
+def _run_convert(args: argparse.Namespace) -> None:
+    from ..utils.bed_writer import names_of
+
+    try:
+        summary = convert(
+            vcf_file=args.vcf,
+            chr_name=args.chr_name,
+            out_prefix=args.out_bfile,
+            ploidy=args.ploidy,
+            haploid_samples=None if args.haploid is None else names_of(args.haploid),
+            samples=None if args.samples is None else names_of(args.samples),
+            start=args.start,
+            end=args.end,
+            append=args.append,
+            skip_multiallelic=args.skip_multiallelic,
+        )
+    except ValueError as exc:
+        args.convert_parser.error(str(exc))
+    print(json.dumps(summary))
+
+
+def add_convert_parser(subparsers) -> None:
+    parser = subparsers.add_parser(
+        "convert", help="Write one chromosome of a VCF as a PLINK 1 binary fileset, encoded on the GPU.",
+        description="Write the calls of one chromosome of a VCF as a PLINK 1 binary fileset (PREFIX.bed + PREFIX.bim + PREFIX.fam) "
+        "with A2 = REF and A1 = ALT: no allele is swapped by its frequency. " + PROMISE + " The VCF is read without ancestral "
+        "alleles; polarisation happens when the fileset is scored, from the .bim alleles.",
+    )  # fmt: skip
+    parser.add_argument("--vcf", type=existed_file, required=True, metavar="FILE", help="Path to the VCF file: plain, gzip or bgzip text.")
+    parser.add_argument("--chr-name", dest="chr_name", type=str, required=True, metavar="C", help="Chromosome to write; one per call.")
+    parser.add_argument("--out-bfile", dest="out_bfile", type=str, required=True, metavar="PREFIX",
+                        help="Prefix of the fileset to write. An existing PREFIX.bed is refused without --append.")  # fmt: skip
+    parser.add_argument("--ploidy", type=int, choices=(1, 2), default=2, help="Ploidy the samples are read at. Default: 2.")
+    parser.add_argument("--haploid", type=existed_file, default=None, metavar="FILE",
+                        help="File of sample names (first word of each line) that are read at ploidy 1; all others at --ploidy.")  # fmt: skip
+    parser.add_argument("--samples", type=existed_file, default=None, metavar="FILE",
+                        help="File of sample names (first word of each line) to write, in this order. Default: every sample of the VCF in column order.")  # fmt: skip
+    parser.add_argument("--start", type=positive_int, default=None, metavar="N", help="First position to write (inclusive). Default: the chromosome's first.")
+    parser.add_argument("--end", type=positive_int, default=None, metavar="N", help="Last position to write (inclusive). Default: the chromosome's last.")
+    parser.add_argument("--append", action="store_true",
+                        help="Add the rows to an existing fileset of the same samples: chromosome after chromosome into one fileset, or a "
+                        "chromosome larger than the GPU's memory range by range. On an error the files are cut back to what they were.")  # fmt: skip
+    parser.add_argument("--skip-multiallelic", dest="skip_multiallelic", action="store_true",
+                        help="Drop and count the records whose ALT holds more than one allele instead of refusing the file.")  # fmt: skip
+    parser.set_defaults(runner=_run_convert, convert_parser=parser)

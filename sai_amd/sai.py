@@ -313,6 +313,18 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
         release_buffers(Engine.get())
 
 
+def convert(vcf_file: str, chr_name: str, out_prefix: str, ploidy: int = 2, haploid_samples=None, samples=None, start: int = None,
+            end: int = None, append: bool = False, skip_multiallelic: bool = False) -> dict:  # fmt: skip
+    """Write one chromosome of a VCF (plain, gzip or bgzip) as the PLINK 1 fileset ``out_prefix``, encoded on the GPU:
+    not a command of the reference.  Reading the fileset at the ploidies it was written with gives the block the VCF
+    reader gives, byte for byte, so ``score`` on it writes the same files -- from either layout.  The arguments, the
+    summary it returns and the refusals: ``utils.bed_writer.convert``."""
+    from .utils.bed_writer import convert as write_fileset
+
+    return write_fileset(vcf_file, chr_name, out_prefix, ploidy=ploidy, haploid_samples=haploid_samples, samples=samples, start=start, end=end,
+                         append=append, skip_multiallelic=skip_multiallelic)  # fmt: skip
+
+
 def outlier(score_file: str, output_prefix: str, quantile: float) -> None:
     """Per statistic column of a score table, write the rows beyond the ``quantile`` of that
     column to ``{output_prefix}.{column}.{quantile}.outliers.tsv`` (sai.py:154-230): columns
