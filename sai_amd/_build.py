@@ -33,6 +33,7 @@ HOST_UNITS = [
     "eigenstrat/eigenstrat_index.cpp",
     "pgen/pgen_index.cpp",
     "pgen/pgen_pack2_host.cpp",
+    "pgen/pgen_encode_host.cpp",
     "bcf/bcf_index.cpp",
     "bcf/bcf_feed.cpp",
     "bcf/csi_index.cpp",
@@ -59,6 +60,7 @@ UNITS = [
     "eigenstrat/geno_transpose.hip",
     "pgen/pgen_decode.hip",
     "pgen/pgen_pack2.hip",
+    "pgen/pgen_encode.hip",
     "bcf/bcf_decode.hip",
     "bcf/bcf_walk.hip",
     "packed_stats/packed2_freqs.hip",
@@ -198,6 +200,7 @@ def build(force: bool = False, sanitize: bool = False) -> None:
 
     for module in family_modules():  # every symbol of include/saihip.h and of each include/saihip_X.h resolves
         module.load()
-    from sai_amd.utils import bed_writer  # ... and the converter's, declared in csrc/plink/bed_export.hpp and bound where they are used
+    from sai_amd.utils import bed_writer, pgen_writer  # ... and the converters', declared in csrc/plink/bed_export.hpp and csrc/pgen/pgen_export.hpp
 
     bed_writer.load()
+    pgen_writer.load()

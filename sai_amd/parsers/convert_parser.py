@@ -1,4 +1,4 @@
-"""``sai convert`` sub-command: a VCF's calls written as a PLINK 1 fileset.  Not a command of the reference."""
+"""``sai convert`` sub-command: a VCF's calls written as a PLINK 1 or a PLINK 2 fileset.  Not a command of the reference."""
 
 from __future__ import annotations
 
@@ -10,6 +10,8 @@ from .argument_validation import existed_file, positive_int
 
 PROMISE = ("Reading the fileset at the ploidies it was written with gives the block the VCF reader gives, byte for byte, "
            "so `sai score` on it writes the same files as on the VCF.")  # fmt: skip
+PGEN_NOTE = ("The .pgen rules were written from memory of the specification: the output is read back by this project's readers and equals "
+             "its test writer's, and has not been opened with plink2.")  # fmt: skip
 
 
 def _run_convert(args: argparse.Namespace) -> None:
@@ -20,6 +22,7 @@ def _run_convert(args: argparse.Namespace) -> None:
             vcf_file=args.vcf,
             chr_name=args.chr_name,
             out_prefix=args.out_bfile,
+            out_pfile=args.out_pfile,
             ploidy=args.ploidy,
             haploid_samples=None if args.haploid is None else names_of(args.haploid),
             samples=None if args.samples is None else names_of(args.samples),
@@ -35,15 +38,20 @@ def _run_convert(args: argparse.Namespace) -> None:
 
 def add_convert_parser(subparsers) -> None:
     parser = subparsers.add_parser(
-        "convert", help="Write one chromosome of a VCF as a PLINK 1 binary fileset, encoded on the GPU.",
+        "convert", help="Write one chromosome of a VCF as a PLINK 1 or PLINK 2 binary fileset, encoded on the GPU.",
         description="Write the calls of one chromosome of a VCF as a PLINK 1 binary fileset (PREFIX.bed + PREFIX.bim + PREFIX.fam) "
-        "with A2 = REF and A1 = ALT: no allele is swapped by its frequency. " + PROMISE + " The VCF is read without ancestral "
-        "alleles; polarisation happens when the fileset is scored, from the .bim alleles.",
+        "with A2 = REF and A1 = ALT: no allele is swapped by its frequency; or, with --out-pfile, as a PLINK 2 fileset (PREFIX.pgen + "
+        "PREFIX.pvar + PREFIX.psam), whose records are compressed on the GPU to about a third of the .bed. " + PROMISE + " The VCF is "
+        "read without ancestral alleles; polarisation happens when the fileset is scored, from the .bim or .pvar alleles. " + PGEN_NOTE,
     )  # fmt: skip
     parser.add_argument("--vcf", type=existed_file, required=True, metavar="FILE", help="Path to the VCF file: plain, gzip or bgzip text.")
     parser.add_argument("--chr-name", dest="chr_name", type=str, required=True, metavar="C", help="Chromosome to write; one per call.")
-    parser.add_argument("--out-bfile", dest="out_bfile", type=str, required=True, metavar="PREFIX",
-                        help="Prefix of the fileset to write. An existing PREFIX.bed is refused without --append.")  # fmt: skip
+    out = parser.add_mutually_exclusive_group(required=True)
+    out.add_argument("--out-bfile", dest="out_bfile", type=str, default=None, metavar="PREFIX",
+                     help="Prefix of the PLINK 1 fileset to write. An existing PREFIX.bed is refused without --append.")  # fmt: skip
+    out.add_argument("--out-pfile", dest="out_pfile", type=str, default=None, metavar="PREFIX",
+                     help="Prefix of the PLINK 2 fileset to write. An existing PREFIX.pgen is refused, and so is --append: the record table "
+                     "of a .pgen sits at the front of the file. Write one fileset per chromosome, or use --out-bfile.")  # fmt: skip
     parser.add_argument("--ploidy", type=int, choices=(1, 2), default=2, help="Ploidy the samples are read at. Default: 2.")
     parser.add_argument("--haploid", type=existed_file, default=None, metavar="FILE",
                         help="File of sample names (first word of each line) that are read at ploidy 1; all others at --ploidy.")  # fmt: skip

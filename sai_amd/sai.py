@@ -313,16 +313,24 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
         release_buffers(Engine.get())
 
 
-def convert(vcf_file: str, chr_name: str, out_prefix: str, ploidy: int = 2, haploid_samples=None, samples=None, start: int = None,
-            end: int = None, append: bool = False, skip_multiallelic: bool = False) -> dict:  # fmt: skip
-    """Write one chromosome of a VCF (plain, gzip or bgzip) as the PLINK 1 fileset ``out_prefix``, encoded on the GPU:
-    not a command of the reference.  Reading the fileset at the ploidies it was written with gives the block the VCF
-    reader gives, byte for byte, so ``score`` on it writes the same files -- from either layout.  The arguments, the
-    summary it returns and the refusals: ``utils.bed_writer.convert``."""
-    from .utils.bed_writer import convert as write_fileset
+def convert(vcf_file: str, chr_name: str, out_prefix: str = None, ploidy: int = 2, haploid_samples=None, samples=None, start: int = None,
+            end: int = None, append: bool = False, skip_multiallelic: bool = False, out_pfile: str = None) -> dict:  # fmt: skip
+    """Write one chromosome of a VCF (plain, gzip or bgzip) as the PLINK 1 fileset ``out_prefix`` (.bed / .bim / .fam)
+    or as the PLINK 2 fileset ``out_pfile`` (.pgen / .pvar / .psam: about a third of the .bed's bytes), encoded on the
+    GPU: not a command of the reference.  Reading the fileset at the ploidies it was written with gives the block the
+    VCF reader gives, byte for byte, so ``score`` on it writes the same files -- from either layout.  The arguments,
+    the summary it returns and the refusals: ``utils.bed_writer.convert`` and ``utils.pgen_writer.convert``.  The
+    ``.pgen`` rules were written from memory of the specification: the output is read back by this project's readers
+    and equals its test writer's, and has not been opened with plink2."""
+    if (out_prefix is None) == (out_pfile is None):
+        raise ValueError("convert writes one fileset: name either out_prefix (PLINK 1) or out_pfile (PLINK 2)")
+    if out_pfile is not None:
+        from .utils.pgen_writer import convert as write_fileset
+    else:
+        from .utils.bed_writer import convert as write_fileset
 
-    return write_fileset(vcf_file, chr_name, out_prefix, ploidy=ploidy, haploid_samples=haploid_samples, samples=samples, start=start, end=end,
-                         append=append, skip_multiallelic=skip_multiallelic)  # fmt: skip
+    return write_fileset(vcf_file, chr_name, out_prefix if out_pfile is None else out_pfile, ploidy=ploidy, haploid_samples=haploid_samples,
+                         samples=samples, start=start, end=end, append=append, skip_multiallelic=skip_multiallelic)  # fmt: skip
 
 
 def outlier(score_file: str, output_prefix: str, quantile: float) -> None:

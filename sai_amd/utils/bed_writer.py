@@ -20,11 +20,13 @@ under include/, and this module -- their only caller -- binds them, with a versi
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import queue
 import threading
 import time
+import types
 from typing import Optional, Sequence
 
 import numpy as np
@@ -220,8 +222,9 @@ class _Target:
                     os.remove(p)
 
 
-def _refuse_unfit(vcf_file, status, pos, samples, ploidies, dosage_at) -> None:
-    """The first flagged row of ``status`` as the converter's ValueError; ``dosage_at(row, slot)`` fetches the value."""
+def _refuse_unfit(vcf_file, status, pos, samples, ploidies, dosage_at, row=".bed row") -> None:
+    """The first flagged row of ``status`` as the converter's ValueError; ``dosage_at(row, slot)`` fetches the value;
+    ``row`` names what a row is written as."""
     bad = np.flatnonzero(status)
     if bad.size == 0:
         return
@@ -231,7 +234,7 @@ def _refuse_unfit(vcf_file, status, pos, samples, ploidies, dosage_at) -> None:
     slot = len(samples) - st
     raise ValueError(
         f"{vcf_file}: the call of sample {samples[slot]} at position {int(pos[k])} has dosage {int(dosage_at(k, slot))} at ploidy {int(ploidies[slot])}: "
-        "a .bed row holds 0, 1, 2 or a wholly missing call at ploidy 2 and 0, 1 or a missing call at ploidy 1 "
+        f"a {row} holds 0, 1, 2 or a wholly missing call at ploidy 2 and 0, 1 or a missing call at ploidy 1 "
         "(a half-missing call, a third allele or another ploidy does not fit)"
     )
 
@@ -340,25 +343,18 @@ def _write_rows_device(eng, dos, uniform, per_slot, target, ms):
     return status.cpu().numpy(), written
 
 
-def convert(vcf_file: str, chr_name: str, out_prefix: str, ploidy: int = 2, haploid_samples: Optional[Sequence[str]] = None,
-            samples: Optional[Sequence[str]] = None, start: Optional[int] = None, end: Optional[int] = None, append: bool = False,
-            skip_multiallelic: bool = False) -> dict:  # fmt: skip
-    """Write the records of ``chr_name`` (inside [start, end]) of a plain, gzip or bgzip VCF as the PLINK 1 fileset
-    ``out_prefix``; see the module's text for what the fileset promises.  ``samples`` = the names to write, in this
-    order (default: every sample of the file in column order); those of ``haploid_samples`` are read at ploidy 1, all
-    others at ``ploidy``.  ``append`` adds the rows to an existing fileset of the same samples (22 chromosomes into one
-    fileset; a chromosome range by range).  ``skip_multiallelic`` drops and counts the records whose ALT holds a comma
-    instead of refusing them.  Returns ``{"rows_written", "rows_skipped", "samples", "bytes", "ms": {phase: ms}}``.
-    Every refusal is a ValueError that names the file and the cause and leaves nothing behind."""
-    t_all = time.perf_counter()
-    vcf_file, chr_name, out_prefix = os.fspath(vcf_file), str(chr_name), os.fspath(out_prefix)
-    if out_prefix.endswith(".bed"):
-        out_prefix = out_prefix[: -len(".bed")]
+# the words a refusal names the output by: the shared steps serve this module and utils/pgen_writer.py
+_BED_WORDS = dict(fileset="PLINK 1 fileset", sample_file=".fam", row=".bed row")
+
+
+def _samples_to_write(vcf_file, ploidy, samples, haploid_samples, words):
+    """The checks of the input and of the sample lists that come before anything is read or written.
+    -> (names of the #CHROM line, names to write, their ploidies)"""
     kind = filesets.name_of(vcf_file)
     if kind is not None:
         raise ValueError(f"{vcf_file} is {kind}, already a binary format: `sai score` reads it as it is; `sai convert` takes VCF text (plain, gzip or bgzip)")
     if ploidy not in (1, 2):
-        raise ValueError(f"ploidy {ploidy}: a PLINK 1 fileset holds haploid and diploid calls only (--ploidy 1 or 2)")
+        raise ValueError(f"ploidy {ploidy}: a {words['fileset']} holds haploid and diploid calls only (--ploidy 1 or 2)")
     if not os.path.isfile(vcf_file):
         raise ValueError(f"{vcf_file} is not found")
     in_file = header_samples(vcf_file)
@@ -370,17 +366,21 @@ def convert(vcf_file: str, chr_name: str, out_prefix: str, ploidy: int = 2, hapl
         raise ValueError(f"samples not found in {vcf_file}: {missing[0]}")
     if len(set(names)) != len(names):
         twice = next(s for s in names if names.count(s) > 1)
-        raise ValueError(f"sample {twice} is asked for twice: a .fam names a sample once")
+        raise ValueError(f"sample {twice} is asked for twice: a {words['sample_file']} names a sample once")
     if not names:
         raise ValueError(f"{vcf_file} has no sample to write")
     hap = set(haploid)
-    ploidies = [1 if s in hap else int(ploidy) for s in names]
-    row_bytes = (len(names) + 3) // 4
-    target = _Target(out_prefix, append, names, row_bytes)
-    ms = dict(read=0.0, site_scan=0.0, encode=0.0, d2h=0.0, write=0.0)
+    return in_file, names, [1 if s in hap else int(ploidy) for s in names]
+
+
+@contextlib.contextmanager
+def _calls(vcf_file, chr_name, in_file, names, ploidies, start, end, skip_multiallelic, ms, words):
+    """The block of the rows to write, read with the VCF readers while a host thread scans the site columns, the two
+    checked against each other and the multiallelic records refused or dropped.  Yields an object with ``host``,
+    ``eng``, ``n_threads``, ``pos`` and ``dos`` (the rows to write), ``sites`` (every row of the region) and ``skip``;
+    the site columns are closed on the way out."""
     host = os.environ.get("SAI_AMD_INGEST") == "host"
     n_threads = default_threads()
-
     scanned = {}
 
     def scan():
@@ -431,7 +431,7 @@ def convert(vcf_file: str, chr_name: str, out_prefix: str, ploidy: int = 2, hapl
         if sites.multi.any():
             if not skip_multiallelic:
                 k = int(np.flatnonzero(sites.multi)[0])
-                raise ValueError(f"{vcf_file}: the record at position {int(pos[k])} of chromosome {chr_name} has more than one ALT allele, and a .bed row "
+                raise ValueError(f"{vcf_file}: the record at position {int(pos[k])} of chromosome {chr_name} has more than one ALT allele, and a {words['row']} "
                                  f"holds two alleles ({int(sites.multi.sum())} such records: --skip-multiallelic drops and counts them)")  # fmt: skip
             skip = sites.multi
             keep = np.flatnonzero(skip == 0)
@@ -442,25 +442,48 @@ def convert(vcf_file: str, chr_name: str, out_prefix: str, ploidy: int = 2, hapl
                 dos = np.ascontiguousarray(dos[keep])
             else:
                 dos = dos.index_select(0, torch.from_numpy(keep).to(eng.device))
+        yield types.SimpleNamespace(host=host, eng=eng, n_threads=n_threads, pos=pos, dos=dos, sites=sites, skip=skip)
+    finally:
+        if sites is not None:
+            sites.close()
+
+
+def convert(vcf_file: str, chr_name: str, out_prefix: str, ploidy: int = 2, haploid_samples: Optional[Sequence[str]] = None,
+            samples: Optional[Sequence[str]] = None, start: Optional[int] = None, end: Optional[int] = None, append: bool = False,
+            skip_multiallelic: bool = False) -> dict:  # fmt: skip
+    """Write the records of ``chr_name`` (inside [start, end]) of a plain, gzip or bgzip VCF as the PLINK 1 fileset
+    ``out_prefix``; see the module's text for what the fileset promises.  ``samples`` = the names to write, in this
+    order (default: every sample of the file in column order); those of ``haploid_samples`` are read at ploidy 1, all
+    others at ``ploidy``.  ``append`` adds the rows to an existing fileset of the same samples (22 chromosomes into one
+    fileset; a chromosome range by range).  ``skip_multiallelic`` drops and counts the records whose ALT holds a comma
+    instead of refusing them.  Returns ``{"rows_written", "rows_skipped", "samples", "bytes", "ms": {phase: ms}}``.
+    Every refusal is a ValueError that names the file and the cause and leaves nothing behind."""
+    t_all = time.perf_counter()
+    vcf_file, chr_name, out_prefix = os.fspath(vcf_file), str(chr_name), os.fspath(out_prefix)
+    if out_prefix.endswith(".bed"):
+        out_prefix = out_prefix[: -len(".bed")]
+    in_file, names, ploidies = _samples_to_write(vcf_file, ploidy, samples, haploid_samples, _BED_WORDS)
+    row_bytes = (len(names) + 3) // 4
+    target = _Target(out_prefix, append, names, row_bytes)
+    ms = dict(read=0.0, site_scan=0.0, encode=0.0, d2h=0.0, write=0.0)
+    with _calls(vcf_file, chr_name, in_file, names, ploidies, start, end, skip_multiallelic, ms, _BED_WORDS) as calls:
+        pos, dos, sites = calls.pos, calls.dos, calls.sites
         uniform, per_slot = _ploidy_arguments(ploidies)
         try:
-            if host:
-                status, written = _write_rows_host(np.ascontiguousarray(dos), uniform, per_slot, target, ms, n_threads)
+            if calls.host:
+                status, written = _write_rows_host(np.ascontiguousarray(dos), uniform, per_slot, target, ms, calls.n_threads)
                 dosage_at = lambda k, s: dos[k, s]  # noqa: E731
             else:
-                status, written = _write_rows_device(eng, dos.contiguous(), uniform, per_slot, target, ms)
+                status, written = _write_rows_device(calls.eng, dos.contiguous(), uniform, per_slot, target, ms)
                 dosage_at = lambda k, s: dos[k, s].item()  # noqa: E731
             _refuse_unfit(vcf_file, status, pos, names, ploidies, dosage_at)
             t0 = time.perf_counter()
-            target.write_text(sites.bim_text(skip), names)
+            target.write_text(sites.bim_text(calls.skip), names)
             ms["write"] += (time.perf_counter() - t0) * 1e3
             target.commit()
         except BaseException:
             target.rollback()
             raise
-    finally:
-        if sites is not None:
-            sites.close()
     ms["total"] = (time.perf_counter() - t_all) * 1e3
     return {"rows_written": int(len(pos)), "rows_skipped": int(sites.n_rows - len(pos)), "samples": len(names), "bytes": int(written) + (0 if target.append else 3),
             "ms": {k: round(v, 3) for k, v in ms.items()}}  # fmt: skip
