@@ -134,14 +134,24 @@ def span_batches(rec, base, cap: int, read_through: int, data_path: str):
     rec_at = at_stream[np.searchsorted(offs, rec_off)]
     rec_end = rec_at + rec_len
     base_at = np.where(has_base, at_stream[np.searchsorted(offs, np.where(has_base, base[:, 0], offs[0]))], -1)
+    def too_small(k: int) -> ValueError:
+        front = int(base[k, 1]) if has_base[k] else 0
+        return ValueError(f"SAI_AMD_INGEST_BUFFER of {cap} bytes is smaller than one record of {data_path} "
+                          f"({int(rec_len[k])} bytes{f' and its base of {front}' if front else ''})")  # fmt: skip
+
+    # A row and its base never fit a smaller buffer, whichever batch the row falls into: with the base inside the
+    # batch both are staged, with the base before it the base is read to the front.  So the first row that is too
+    # long is refused here, before the first batch is yielded, and not after the rows before it have been decoded.
+    short = np.flatnonzero(rec_len + np.where(has_base, base[:, 1], 0) > cap)
+    if short.size:
+        raise too_small(int(short[0]))
     k0 = 0
     while k0 < n_rows:
         lo = int(rec_at[k0])
         front = int(base[k0, 1]) if has_base[k0] else 0  # the first row's base, read on its own
         k1 = int(np.searchsorted(rec_end, lo + cap - front, side="right"))
-        if k1 <= k0:
-            raise ValueError(f"SAI_AMD_INGEST_BUFFER of {cap} bytes is smaller than one record of {data_path} "
-                             f"({int(rec_len[k0])} bytes{f' and its base of {front}' if front else ''})")  # fmt: skip
+        if k1 <= k0:  # cannot be, after the check above: but a batch without a row would never end the loop
+            raise too_small(k0)
         hi = int(rec_end[k1 - 1])
         reads = [(0, int(base[k0, 0]), front)] if front else []
         j = int(np.searchsorted(range_stream, lo, side="right")) - 1
