@@ -82,7 +82,7 @@ enum sai_status {
 
 /* comparison operators of the source-frequency conditions (stat_utils.py:133-139) */
 enum sai_op { SAI_OP_EQ = 0, SAI_OP_LT = 1, SAI_OP_GT = 2, SAI_OP_LE = 3, SAI_OP_GE = 4 };
-enum sai_freq_mode { SAI_FREQ_DENSE = 0, SAI_FREQ_CANDIDATES = 1 }; /* see sai_site_pass */
+enum sai_freq_mode { SAI_FREQ_DENSE = 0, SAI_FREQ_CANDIDATES = 1, SAI_FREQ_CANDIDATES_READ_ALL = 2 }; /* see sai_site_pass */
 
 typedef struct sai_ctx sai_ctx;
 
@@ -158,6 +158,9 @@ int sai_site_counts(sai_ctx* ctx, int64_t n_sites, int32_t n_pops, const sai_pop
  * ceil(n_sites / 64) * 3 * n_sets (-1 on bad arguments). */
 int64_t sai_plane_words(int64_t n_sites, int32_t n_sets);
 
+/* Target individuals from which sai_site_pass may leave target rows unread (see there). */
+int32_t sai_skip_min_tgt_ind(void);
+
 /* Kernels 1+2 fused (the fast path when there are at most SAI_FUSED_SETS parameter sets): one pass over the
  * genotypes that also evaluates sai_site_flags' per-site decision for each set at the end of every
  * tile, while the counts are still on chip.  `counts` may be NULL (then the 8 bytes per site and
@@ -169,6 +172,13 @@ int64_t sai_plane_words(int64_t n_sites, int32_t n_sets);
  * the OR of the conditions; see the top of this header) and leaves the rest of the buffer untouched
  * (dense 8-byte stores interleaved with the genotype stream cost about 10 % of the pass on MI355X,
  * a tile's candidates in slots of their own a fifth of that for sets as loose as C5's).
+ * With SAI_FREQ_CANDIDATES, counts == NULL, every set polarised by ancestral alleles, fewer than four sets and a
+ * target of at least sai_skip_min_tgt_ind() individuals (at most 3 968 per population), the pass streams a tile's
+ * sources and ref first and reads the target's rows only where some site passes the ref and source conditions: no
+ * other site can have a condition bit up, so the outputs are the same bit for bit, and the pass moves about half of
+ * the bytes where candidates are rare.  SAI_FREQ_CANDIDATES_READ_ALL (sai_site_pass only) is SAI_FREQ_CANDIDATES
+ * with every population read in every tile -- for a caller that times the memory traffic itself; the environment
+ * variable SAI_TGT_SKIP=0 does the same for every call of the process (A/B runs of one build).
  * Streams: a launch of many multi-wavefront workgroups (sai_window_stats, sai_site_flags, any large kernel)
  * that waits in THIS pass's stream behind the running pass costs the pass ~6 % (profiles/history/r04_lone_pass.txt);
  * enqueue what follows on a second stream behind an event wait. */

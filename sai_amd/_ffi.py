@@ -25,7 +25,7 @@ SAI_ERR_ARG = -1
 SAI_ERR_HIP = -2
 SAI_ERR_NO_DEVICE = -3
 SAI_ERR_UNSUPPORTED = -4  # enum sai_status
-FREQ_MODES = {"dense": 0, "candidates": 1}  # enum sai_freq_mode
+FREQ_MODES = {"dense": 0, "candidates": 1, "candidates_read_all": 2}  # enum sai_freq_mode
 SAI_ABI_VERSION = 16
 
 OPS = {"=": 0, "<": 1, ">": 2, "<=": 3, ">=": 4}
@@ -99,6 +99,7 @@ SIGNATURES = {
     "sai_tile_from_site_major": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _p]),
     "sai_site_counts": (C.c_int, [_p, _i64, _i32, C.POINTER(SaiPop), _p, _p]),
     "sai_plane_words": (_i64, [_i64, _i32]),
+    "sai_skip_min_tgt_ind": (_i32, []),
     "sai_site_pass": (
         C.c_int,
         [_p, _i64, _i32, C.POINTER(SaiPop), _p, _i32, C.POINTER(SaiParams), _i32, _p, _p, _i64, _p],

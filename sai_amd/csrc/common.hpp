@@ -134,6 +134,12 @@ inline int site_pass_waves_per_cu(const sai_ctx* ctx, int64_t n_tiles, int32_t n
   return wide && n_tiles >= static_cast<int64_t>(ctx->n_cu) * 8 * 32 ? 8 : kStreamWavesPerCu;
 }
 
+// Target individuals from which the fused pass leaves the target's rows unread in tiles where no site passes the
+// ref and source conditions (site_pass.hip, the SKIP form).  It MUST stay above 200: the bench line's contract
+// (tests/test_hip_sharded.py) pins C2's 200 / 200 / 2 pass to reading every byte, 1.0 <= traffic / algorithmic
+// bytes < 1.01.  The value is the narrowest width of the sweep in profiles/tgt_skip_ab.txt, a multiple of 16.
+constexpr int kSkipMinTgtInd = 256;
+
 // The site pass with DD's terms riding along (site_pass_dd.hip) is built for three waves per SIMD (one or two
 // source individuals) or two (three or four), and takes them: unlike the plain pass it has arithmetic to hide
 // behind its loads (C3 shape, two source individuals: 3.26 ms at 12 waves per CU, 3.45 at 8; three source

@@ -56,6 +56,39 @@ __global__ __launch_bounds__(256) void site_flags_kernel(FlagArgs a) {
 
 static_assert(sizeof(CountsArgs) + sizeof(FusedArgs) <= 4096, "kernel arguments exceed the kernarg segment");
 
+// The vote of the skipping form: can a condition bit of this lane's site still be up, whatever the target holds?
+// eval_site's set-by-set decision for sets polarised by ancestral alleles -- the same f64 quotients and compares --
+// without the target's term of `valid`: exactly the sites whose bit is up once the target proves valid, and no others.
+template <typename GetCounts>
+__device__ __forceinline__ bool target_may_matter(int n_pops, const FusedArgs& fa, GetCounts get, bool live) {
+  double f[kMaxPops];
+  bool valid = live;
+#pragma unroll
+  for (int p = 0; p < kMaxPops; ++p) {
+    if (p != 1 && p < n_pops) {
+      const uint2 c = get(p);
+      const int64_t den = static_cast<int64_t>(c.y) * fa.ploidy[p];
+      const double v = den > 0 ? static_cast<double>(c.x) / static_cast<double>(den)
+                               : std::numeric_limits<double>::quiet_NaN();
+      f[p] = v;
+      valid = valid && (v >= 0.0) && (v <= 1.0);
+    } else {
+      f[p] = 0.0;
+    }
+  }
+  const int n_src = n_pops - 2;
+  bool may = false;
+  for (int s = 0; s < fa.n_sets; ++s) {
+    const DevSet& ps = fa.es.sets[s];
+    bool hit = true;
+#pragma unroll
+    for (int k = 0; k < SAI_FUSED_SRC; ++k)
+      if (k < n_src) hit = hit && cmp_op(ps.op[k], f[2 + k], ps.y[k]);
+    may = may || (hit && (f[0] < ps.w));
+  }
+  return valid && may;
+}
+
 // MULTI: some population has more than 16 * kChunkIters individuals, so the packed fields are
 // widened several times per population (keeps 32 more registers live across the load loop).
 // FUSED: evaluate the parameter sets at the end of each tile (site_flags folded in).
@@ -66,8 +99,15 @@ static_assert(sizeof(CountsArgs) + sizeof(FusedArgs) <= 4096, "kernel arguments 
 // predicate table of site_eval.hpp the per-site decision no longer decides the grid: the usual form at 12
 // waves per CU gives C5's pipelined step 3.09 ms where that form gave 3.15 with the set-by-set decision and
 // 3.41 with the table -- profiles/r05_c5_grid.txt -- and the form is gone.)
-template <bool MULTI, bool FUSED>
+// SKIP (fused, not MULTI, candidates' frequencies only, every set polarised by ancestral alleles, set-by-set form):
+// a condition bit can only be up where ref_freq < w and the sources' comparisons hold -- the target enters
+// tgt_freq at such sites and the validity test, which can only CLEAR a bit.  The tile's sources and ref are
+// streamed first, lane = site votes whether some set can still pass, and the target's rows -- half of C3's
+// bytes -- are read only in tiles where a lane said yes (one site in 1 000 passes: 6 % of C3's tiles); the
+// other tiles' rows are stored as zeros.  The outputs are the other form's bit for bit.
+template <bool MULTI, bool FUSED, bool SKIP = false>
 __global__ __launch_bounds__(64, MULTI ? 4 : 5) void site_counts_kernel(CountsArgs a, FusedArgs fa) {
+  static_assert(!SKIP || (FUSED && !MULTI), "the skipping form is the usual fused form's");
   // FUSED: the butterfly leaves lane l with site (l%4)*16 + l/4 of the tile; each lane parks those
   // {alt_sum, n_called} per population in LDS AT ITS SITE'S INDEX, and once all populations of the
   // tile are done lane l takes site l back and evaluates the parameter sets for it -- lanes in site
@@ -82,7 +122,19 @@ __global__ __launch_bounds__(64, MULTI ? 4 : 5) void site_counts_kernel(CountsAr
   for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const int lane = threadIdx.x;
     const int r = lane >> 2;
-    for (int p = 0; p < a.n_pops; ++p) {
+    // SKIP: sources, ref, the vote, then the target (p = 1) -- or nothing
+    int k = 0;
+    for (; k < a.n_pops; ++k) {
+      const int p = !SKIP ? k : k + 2 < a.n_pops ? k + 2 : k + 2 == a.n_pops ? 0 : 1;
+      if (SKIP && p == 1) {
+        wave_lds_fence();
+        if (__ballot(target_may_matter(a.n_pops, fa, [&](int q) { return stash[q][lane]; },
+                                       tile * kTile + lane < a.n_sites)) == 0ull) {
+          // the row eval_site would have stored: "any" and the sets' conditions all down, no frequency
+          if (lane <= fa.n_sets) __builtin_nontemporal_store(uint64_t{0}, fa.planes + tile * fa.plane_stride + lane);
+          break;
+        }
+      }
       const int n_ind = a.pop[p].n_ind;
       const u32x4* base =
           reinterpret_cast<const u32x4*>(a.pop[p].tiles + tile * static_cast<int64_t>(n_ind) * kTile) + lane;
@@ -139,8 +191,12 @@ __global__ __launch_bounds__(64, MULTI ? 4 : 5) void site_counts_kernel(CountsAr
         cnt = make_uint2(both[0] & 0xFFFFFu, static_cast<uint32_t>(n_ind) - (both[0] >> 20));
       }
       const int64_t site = tile * kTile + (lane & 3) * 16 + r;
-      if (a.counts && site < a.n_sites) store_counts_nt(a.counts + static_cast<int64_t>(p) * a.n_sites + site, cnt);
+      if (!SKIP && a.counts && site < a.n_sites) store_counts_nt(a.counts + static_cast<int64_t>(p) * a.n_sites + site, cnt);
       if (FUSED) stash[p][(lane & 3) * 16 + r] = cnt;
+    }
+    if (SKIP && k < a.n_pops) {  // the target was left unread
+      wave_lds_fence();  // the next tile's counts must not overtake the vote's reads
+      continue;
     }
     if (FUSED) {
       wave_lds_fence();
@@ -160,6 +216,8 @@ int check_plane_stride(int64_t plane_stride, int32_t n_sets) {
     return fail(SAI_ERR_ARG, "plane_stride %lld does not hold %d sets", static_cast<long long>(plane_stride), n_sets);
   return SAI_OK;
 }
+
+extern "C" int32_t sai_skip_min_tgt_ind(void) { return kSkipMinTgtInd; }
 
 extern "C" int64_t sai_plane_words(int64_t n_sites, int32_t n_sets) {
   if (n_sites < 0 || n_sets < 0 || n_sites >= 0x7FFFFFFFll) return -1;
@@ -208,7 +266,7 @@ static int launch_site_counts(sai_ctx* ctx, int64_t n_sites, int32_t n_pops, con
   }
   a.counts = reinterpret_cast<uint2*>(counts);
   fa.n_sets = n_sets;
-  fa.sparse_freq = freq_mode == SAI_FREQ_CANDIDATES;
+  fa.sparse_freq = freq_mode != SAI_FREQ_DENSE;
   fa.with_inv = n_sets > 0 && sets_with_inverted(n_sets, sets_host);
   fa.tgt_freq = tgt_freq;
   fa.planes = planes;
@@ -218,8 +276,16 @@ static int launch_site_counts(sai_ctx* ctx, int64_t n_sites, int32_t n_pops, con
   for (int p = 0; p < n_pops; ++p) individuals += pops[p].n_ind;
   const dim3 grid(stream_grid(ctx, a.n_tiles, site_pass_waves_per_cu(ctx, a.n_tiles, n_sets, n_pops, individuals)));
   hipStream_t st = static_cast<hipStream_t>(stream);
+  // the form that leaves the target unread where no site can pass: only where its outputs are the other form's bit
+  // for bit (the candidates' frequencies alone, no counts, no inverted words -- an inverted bit depends on the
+  // target's validity where the condition is false) and the decision is taken set by set (a call of C5's many
+  // sets has a candidate in every tile); SAI_TGT_SKIP=0: A/B knob, read at every launch
+  const char* skip_env = std::getenv("SAI_TGT_SKIP");
+  const bool skip = n_sets > 0 && !multi && freq_mode == SAI_FREQ_CANDIDATES && !counts && !fa.with_inv &&
+                    !fa.es.use_table && pops[1].n_ind >= kSkipMinTgtInd && !(skip_env && skip_env[0] == '0');
   if (n_sets > 0) {
     if (multi) launch_pass(ctx, site_counts_kernel<true, true>, grid, dim3(64), st, a, fa);
+    else if (skip) launch_pass(ctx, site_counts_kernel<false, true, true>, grid, dim3(64), st, a, fa);
     else launch_pass(ctx, site_counts_kernel<false, true>, grid, dim3(64), st, a, fa);
   } else {
     if (multi) launch_pass(ctx, site_counts_kernel<true, false>, grid, dim3(64), st, a, fa);
@@ -245,7 +311,8 @@ int sai_site_pass(sai_ctx* ctx, int64_t n_sites, int32_t n_pops, const sai_pop* 
                   int32_t n_sets, const sai_params* sets_host, int32_t freq_mode, double* tgt_freq, uint64_t* planes,
                   int64_t plane_stride, void* stream) {
   if (int rc = enter(ctx)) return rc;
-  if (freq_mode != SAI_FREQ_DENSE && freq_mode != SAI_FREQ_CANDIDATES) return fail(SAI_ERR_ARG, "bad freq_mode %d", freq_mode);
+  if (freq_mode != SAI_FREQ_DENSE && freq_mode != SAI_FREQ_CANDIDATES && freq_mode != SAI_FREQ_CANDIDATES_READ_ALL)
+    return fail(SAI_ERR_ARG, "bad freq_mode %d", freq_mode);
   if (n_pops < 2) return fail(SAI_ERR_ARG, "n_pops must be >= 2 (ref, tgt, sources)");
   if (n_sets > kFusedSets)
     return fail(SAI_ERR_UNSUPPORTED, "sai_site_pass carries at most %d parameter sets; use sai_site_counts + sai_site_flags",

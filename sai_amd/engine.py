@@ -667,7 +667,9 @@ class Engine:
         the per-population counts stay on chip unless a ``counts`` tensor is passed.  Returns
         (tgt_freq, flag planes) exactly as ``site_flags(site_counts(pops), ...)`` would; with
         ``freq_mode="candidates"`` tgt_freq is written only where some set's condition bit is up
-        (all that ``window_stats`` reads) and every other entry of ``out[0]`` is left as it was."""
+        (all that ``window_stats`` reads) and every other entry of ``out[0]`` is left as it was -- and a wide
+        target's rows are read only in tiles that hold such a site (saihip.h); ``"candidates_read_all"`` gives the
+        same outputs with every row read (for timing memory traffic: ``placement._PairTimer``)."""
         torch = _torch()
         n_sites = pops[0].n_sites
         if any(p.n_sites != n_sites for p in pops):

@@ -66,7 +66,8 @@ class OutputArena:
 
 class _PairTimer:
     """The fused site pass over two populations with one parameter set no site satisfies (w = 0: nothing is
-    written), timed with events on the current stream."""
+    written), timed with events on the current stream.  ``candidates_read_all``: with no site that passes, the
+    plain candidates mode would leave the second population unread and time the first alone."""
 
     def __init__(self, eng, n_sites: int):
         import torch
@@ -81,7 +82,7 @@ class _PairTimer:
         for k in range(passes + 1):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            self.eng.site_pass([a, b], [1, 1], self.sets, out=self.out, freq_mode="candidates")
+            self.eng.site_pass([a, b], [1, 1], self.sets, out=self.out, freq_mode="candidates_read_all")
             e1.record()
             e1.synchronize()
             if k:

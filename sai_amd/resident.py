@@ -336,7 +336,14 @@ class ResidentScorer:
                     cp.add_site_pass(self.packed, blk.ploidies, [], None, counts=self.counts, packed2=True)
             elif self.fused:
                 cp = eng.plan()
-                cp.add_site_pass(blk.pops, blk.ploidies, self.sets, out, counts=self.counts_out, freq_mode="candidates",
+                # A block of several pieces (a rank's share of a whole-genome job) goes on reading every population in
+                # every tile: an N > 1 bench line takes its traffic as the rank's share BY SITES of the one-GPU job's
+                # stored counters (bench.static_traffic), which holds only while the bytes of a pass scale with its
+                # sites, and tests/test_bench_sharded_cpu.py pins that stored figure above the job's genotype bytes.
+                # A known leftover: the whole-genome job would gain what C3 gains (profiles/tgt_skip_ab.txt).
+                several = blk.segments is not None and len(blk.segments) > 1
+                mode = "candidates_read_all" if several and self.dd_out is None else "candidates"
+                cp.add_site_pass(blk.pops, blk.ploidies, self.sets, out, counts=self.counts_out, freq_mode=mode,
                                  dd=self.dd_out)  # fmt: skip
             elif not self.have_counts:
                 cp = eng.plan()
