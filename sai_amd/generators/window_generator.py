@@ -62,13 +62,16 @@ class WindowGenerator(DataGenerator):
         resident: bool = False,
         preloaded=None,
         layout: str = "int8",
+        *,
+        src_file: str = None,
     ):
         """``resident=True`` (the batched GPU driver, ChunkPreprocessor): the region is streamed to
         the GPU and tokenised there, the populations exist only as tiled blocks in HBM and ``get()``
         is not available; otherwise the populations are host matrices, as in the reference.
         ``preloaded`` = what ``read_data_device`` returned for exactly this region (the caller read it
         before it knew the chunk bounds, ChunkPreprocessor.preload).  ``layout="packed2"`` (with ``resident``): the
-        populations are read as ``PackedPop`` blocks (``read_data_device``)."""
+        populations are read as ``PackedPop`` blocks (``read_data_device``).  ``src_file``: the samples of the ``src``
+        group are read from that file and joined to the others' sites (``sai_amd.site_join``); host matrices only."""
         if win_len <= 0:
             raise ValueError("`win_len` must be greater than 0.")
         if win_step < 0:
@@ -78,6 +81,10 @@ class WindowGenerator(DataGenerator):
         kw = dict(vcf_file=vcf_file, chr_name=chr_name, start=start, end=end, ref_ind_file=ref_ind_file,
                   tgt_ind_file=tgt_ind_file, src_ind_file=src_ind_file, out_ind_file=out_ind_file,
                   ploidy_config=ploidy_config, anc_allele_file=anc_allele_file)  # fmt: skip
+        if src_file is not None:
+            if resident or preloaded is not None:
+                raise ValueError("`src_file` is joined over host matrices only: it cannot be combined with `resident` or `preloaded`.")
+            kw["src_file"] = src_file
         pos_dev = None
         if preloaded is not None:
             results, pos_dev = preloaded

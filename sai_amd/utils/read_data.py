@@ -77,6 +77,8 @@ def read_dosage_data(
     start: int = None,
     end: int = None,
     engine: str = "native",
+    *,
+    src_file: Optional[str] = None,
 ) -> dict[str, tuple[Optional[dict[str, ChromosomeData]], Optional[dict[str, list[str]]]]]:
     """``read_data(..., is_phased=False, filter_*=False, filter_missing=False)``:
     {"ref": (data, samples), "tgt": ..., "src": ..., "outgroup": (data, samples) or (None, None)}.
@@ -87,7 +89,19 @@ def read_dosage_data(
     holds no record.  The VCF is parsed once per distinct ploidy for all groups (the reference
     re-reads it per population) by the native tokenizer of libsaihip (``engine="native"``) or by
     the Python statement of the same rules (``engine="python"``, used by the tests as the
-    cross-check); REF/ALT are not kept (nothing reads them after polarisation)."""
+    cross-check); REF/ALT are not kept (nothing reads them after polarisation).
+
+    ``src_file``: the samples of the ``src`` group are read from that file, those of the other groups from ``vcf_file``,
+    each by its own reader with the same ancestral alleles; the blocks hold the sites both readers kept
+    (``sai_amd.site_join``), and the result carries ``"site_join"``, the join's summary."""
+    if src_file is not None:
+        from ..site_join import join_host_results, require_second_input
+
+        require_second_input(src_file, anc_allele_file)
+        panel = read_dosage_data(vcf_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, None, out_ind_file, anc_allele_file,
+                                 start, end, engine)  # fmt: skip
+        source = read_dosage_data(src_file, chr_name, ploidy_config, None, None, src_ind_file, None, anc_allele_file, start, end, engine)
+        return join_host_results(panel, source, vcf_file, src_file)
     chr_name = str(chr_name)
     samples_by_group = _parse_groups(ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file)
     # one pass per distinct ploidy (normally one or two), each over the samples that need it
