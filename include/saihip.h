@@ -161,6 +161,11 @@ int64_t sai_plane_words(int64_t n_sites, int32_t n_sets);
 /* Target individuals from which sai_site_pass may leave target rows unread (see there). */
 int32_t sai_skip_min_tgt_ind(void);
 
+/* Where the target may be left unread and ref holds at least sai_ref_probe_min_ind() individuals, sai_site_pass reads
+ * the first sai_ref_probe_rows() ref rows of a tile first and the others only where some site can still pass. */
+int32_t sai_ref_probe_rows(void);
+int32_t sai_ref_probe_min_ind(void);
+
 /* Kernels 1+2 fused (the fast path when there are at most SAI_FUSED_SETS parameter sets): one pass over the
  * genotypes that also evaluates sai_site_flags' per-site decision for each set at the end of every
  * tile, while the counts are still on chip.  `counts` may be NULL (then the 8 bytes per site and
@@ -176,7 +181,11 @@ int32_t sai_skip_min_tgt_ind(void);
  * target of at least sai_skip_min_tgt_ind() individuals (at most 3 968 per population), the pass streams a tile's
  * sources and ref first and reads the target's rows only where some site passes the ref and source conditions: no
  * other site can have a condition bit up, so the outputs are the same bit for bit, and the pass moves about half of
- * the bytes where candidates are rare.  SAI_FREQ_CANDIDATES_READ_ALL (sai_site_pass only) is SAI_FREQ_CANDIDATES
+ * the bytes where candidates are rare.  With a ref of at least sai_ref_probe_min_ind() individuals it goes further: ref
+ * and target stay unread in tiles where no site passes the source conditions, and ref is read beyond its first
+ * sai_ref_probe_rows() rows only while some such site's alt sum over the rows read so far, divided by n_ref * ploidy,
+ * is still below its set's w -- the sum only grows and the divisor only shrinks, so no other site can end below w
+ * (SAI_REF_PROBE=0: ref in one piece, for A/B runs of one build).  SAI_FREQ_CANDIDATES_READ_ALL (sai_site_pass only) is SAI_FREQ_CANDIDATES
  * with every population read in every tile -- for a caller that times the memory traffic itself; the environment
  * variable SAI_TGT_SKIP=0 does the same for every call of the process (A/B runs of one build).
  * Streams: a launch of many multi-wavefront workgroups (sai_window_stats, sai_site_flags, any large kernel)

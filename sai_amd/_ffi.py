@@ -100,6 +100,8 @@ SIGNATURES = {
     "sai_site_counts": (C.c_int, [_p, _i64, _i32, C.POINTER(SaiPop), _p, _p]),
     "sai_plane_words": (_i64, [_i64, _i32]),
     "sai_skip_min_tgt_ind": (_i32, []),
+    "sai_ref_probe_rows": (_i32, []),
+    "sai_ref_probe_min_ind": (_i32, []),
     "sai_site_pass": (
         C.c_int,
         [_p, _i64, _i32, C.POINTER(SaiPop), _p, _i32, C.POINTER(SaiParams), _i32, _p, _p, _i64, _p],

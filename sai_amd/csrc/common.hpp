@@ -140,6 +140,18 @@ inline int site_pass_waves_per_cu(const sai_ctx* ctx, int64_t n_tiles, int32_t n
 // bytes < 1.01.  The value is the narrowest width of the sweep in profiles/tgt_skip_ab.txt, a multiple of 16.
 constexpr int kSkipMinTgtInd = 256;
 
+// The SKIP form's probe of ref (site_pass.hip): a tile's first kRefProbeRows ref rows are read as a population of their
+// own, and the others only where some source-matching site's partial alt sum can still end below w.  A multiple of 64:
+// the probe is whole groups of kUnroll wave loads (128 rows: C3 0.48 against 0.40 ms).  kRefProbeMinInd: ref individuals
+// from which the probe is taken; a narrower ref is read in one piece.  The width sweep of profiles/ref_probe_ab.txt:
+// a ref of 64 loses 2 %, 128 gains 18 %, 256 43 %, 512 65 %; a block on which no tile exits (w = 1) pays 3-7 % of its
+// step at 64 and 256 individuals and nothing at 1 000.  kRefProbeWavesPerCu: the probing form's grid where
+// site_pass_waves_per_cu gives 8 (launch_site_counts); a call of kManySets sets or more does not take the form.
+constexpr int kRefProbeRows = 64;
+constexpr int kRefProbeMinInd = 128;
+constexpr int kRefProbeWavesPerCu = 24;
+static_assert(kRefProbeRows % 64 == 0 && kRefProbeMinInd >= kRefProbeRows, "the probe is whole groups of loads inside ref");
+
 // The site pass with DD's terms riding along (site_pass_dd.hip) is built for three waves per SIMD (one or two
 // source individuals) or two (three or four), and takes them: unlike the plain pass it has arithmetic to hide
 // behind its loads (C3 shape, two source individuals: 3.26 ms at 12 waves per CU, 3.45 at 8; three source

@@ -89,6 +89,87 @@ __device__ __forceinline__ bool target_may_matter(int n_pops, const FusedArgs& f
   return valid && may;
 }
 
+// The first vote of the probing form, taken once a tile's sources are counted: bit s is up iff the sources are valid at
+// this lane's site and set s's source comparisons hold -- target_may_matter's quotients and compares without ref's terms.
+template <typename GetCounts>
+__device__ __forceinline__ uint32_t source_hits(int n_pops, const FusedArgs& fa, GetCounts get, bool live) {
+  double f[kMaxPops];
+  bool valid = live;
+#pragma unroll
+  for (int p = 2; p < kMaxPops; ++p) {
+    if (p < n_pops) {
+      const uint2 c = get(p);
+      const int64_t den = static_cast<int64_t>(c.y) * fa.ploidy[p];
+      const double v = den > 0 ? static_cast<double>(c.x) / static_cast<double>(den)
+                               : std::numeric_limits<double>::quiet_NaN();
+      f[p] = v;
+      valid = valid && (v >= 0.0) && (v <= 1.0);
+    } else {
+      f[p] = 0.0;
+    }
+  }
+  const int n_src = n_pops - 2;
+  uint32_t hits = 0;
+  for (int s = 0; s < fa.n_sets; ++s) {
+    const DevSet& ps = fa.es.sets[s];
+    bool hit = valid;
+#pragma unroll
+    for (int k = 0; k < SAI_FUSED_SRC; ++k)
+      if (k < n_src) hit = hit && cmp_op(ps.op[k], f[2 + k], ps.y[k]);
+    hits |= hit ? 1u << s : 0u;
+  }
+  return hits;
+}
+
+// The second vote: ref's alt sum only grows as rows are added (a missing call adds nothing) and its divisor
+// n_called * ploidy is at most n_ref * ploidy, so the final quotient is at least partial_alt / (n_ref * ploidy) -- as
+// doubles too: both terms are exact and the division rounds monotonically.  A set whose w that bound has reached is
+// out; a site with no set left cannot have a bit up.
+__device__ __forceinline__ bool ref_may_pass(const FusedArgs& fa, uint32_t hits, uint32_t partial_alt, int n_ref) {
+  const double bound =
+      static_cast<double>(partial_alt) / static_cast<double>(static_cast<int64_t>(n_ref) * fa.ploidy[0]);
+  bool may = false;
+  for (int s = 0; s < fa.n_sets; ++s) may = may || (((hits >> s) & 1u) != 0u && bound < fa.es.sets[s].w);
+  return may;
+}
+
+// {alt_sum, missing calls} of rows 0 .. n_ind - 1 behind `base`, for site (lane % 4) * 16 + lane / 4.  At most
+// 16 * (kChunkIters + 1) rows: one pass, widened once -- and ONE butterfly for both sums.  A whole population of the
+// forms that are not MULTI, or a piece of ref in the probing form.
+__device__ __forceinline__ uint2 count_piece(const u32x4* base, int n_ind, int r, int lane) {
+  const int n_full = n_ind >> 4;
+  const int n_iter = (n_ind + 15) >> 4;
+  int it = 0;
+  uint32_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0}, ms[4] = {0, 0, 0, 0};
+  accumulate_rows(base, it, n_full, n_full, n_iter, n_ind, r, lo, hi, ms);
+  // a site's alt sum stays below 2^20 and its missing count below 2^12 for the at most 3 984 individuals of this
+  // form, so the two travel through the butterfly in one word: half of the cross-lane work per population, which
+  // is what a tile of NARROW populations is made of (a lone C2: 0.689 against 0.677 of peak; wide populations: the same)
+  static_assert(16 * (kChunkIters + 1) * 255 < (1 << 20) && 16 * (kChunkIters + 1) < (1 << 12), "packed butterfly fields overflow");
+  uint32_t both[16];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    both[4 * j + 0] = lo[j] & 0xFFFFu;
+    both[4 * j + 1] = hi[j] & 0xFFFFu;
+    both[4 * j + 2] = lo[j] >> 16;
+    both[4 * j + 3] = hi[j] >> 16;
+  }
+  if (__ballot((ms[0] | ms[1] | ms[2] | ms[3]) != 0u) != 0ull) {  // wave-uniform: some lane met a missing call
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      both[4 * j + 0] |= (ms[j] & 0xFFu) << 20;
+      both[4 * j + 1] |= ((ms[j] >> 8) & 0xFFu) << 20;
+      both[4 * j + 2] |= ((ms[j] >> 16) & 0xFFu) << 20;
+      both[4 * j + 3] |= (ms[j] >> 24) << 20;
+    }
+  }
+  reduce_scatter_step<16, 32>(both, lane);
+  reduce_scatter_step<8, 16>(both, lane);
+  reduce_scatter_step<4, 8>(both, lane);
+  reduce_scatter_step<2, 4>(both, lane);
+  return make_uint2(both[0] & 0xFFFFFu, both[0] >> 20);
+}
+
 // MULTI: some population has more than 16 * kChunkIters individuals, so the packed fields are
 // widened several times per population (keeps 32 more registers live across the load loop).
 // FUSED: evaluate the parameter sets at the end of each tile (site_flags folded in).
@@ -105,9 +186,16 @@ __device__ __forceinline__ bool target_may_matter(int n_pops, const FusedArgs& f
 // streamed first, lane = site votes whether some set can still pass, and the target's rows -- half of C3's
 // bytes -- are read only in tiles where a lane said yes (one site in 1 000 passes: 6 % of C3's tiles); the
 // other tiles' rows are stored as zeros.  The outputs are the other form's bit for bit.
-template <bool MULTI, bool FUSED, bool SKIP = false>
+// PROBE (SKIP, a ref of at least kRefProbeMinInd individuals): what the result uses of ref is one bit per site,
+// ref_freq < w, and only at sites where the sources' comparisons hold.  The sources are streamed first and the
+// lanes vote (source_hits): a tile without such a site reads neither ref nor target.  Then ref's first PROBE rows are
+// counted as a population of their own and the lanes vote again (ref_may_pass): the rows beyond are read only where
+// some site's partial sum has not reached w yet, and their counts added -- from there on the tile is the SKIP form's,
+// on the counts a full read gives.  C3: 6.6 % of the tiles go on beyond 64 rows, 6.2 % hold a candidate.
+template <bool MULTI, bool FUSED, bool SKIP = false, int PROBE = 0>
 __global__ __launch_bounds__(64, MULTI ? 4 : 5) void site_counts_kernel(CountsArgs a, FusedArgs fa) {
   static_assert(!SKIP || (FUSED && !MULTI), "the skipping form is the usual fused form's");
+  static_assert(PROBE == 0 || SKIP, "the probing form is the skipping form's");
   // FUSED: the butterfly leaves lane l with site (l%4)*16 + l/4 of the tile; each lane parks those
   // {alt_sum, n_called} per population in LDS AT ITS SITE'S INDEX, and once all populations of the
   // tile are done lane l takes site l back and evaluates the parameter sets for it -- lanes in site
@@ -122,9 +210,45 @@ __global__ __launch_bounds__(64, MULTI ? 4 : 5) void site_counts_kernel(CountsAr
   for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const int lane = threadIdx.x;
     const int r = lane >> 2;
+    if constexpr (PROBE > 0) {  // sources, vote, ref's first rows, vote, ref's other rows, vote, target -- or nothing from a vote on
+      const int mine = (lane & 3) * 16 + r;  // the site whose counts the butterfly leaves in this lane
+      const bool live = tile * kTile + lane < a.n_sites;
+      auto rows_of = [&](int p) {
+        return reinterpret_cast<const u32x4*>(a.pop[p].tiles + tile * static_cast<int64_t>(a.pop[p].n_ind) * kTile) + lane;
+      };
+      auto count_pop = [&](int p) {
+        const uint2 c = count_piece(rows_of(p), a.pop[p].n_ind, r, lane);
+        return make_uint2(c.x, static_cast<uint32_t>(a.pop[p].n_ind) - c.y);
+      };
+      for (int p = 2; p < a.n_pops; ++p) stash[p][mine] = count_pop(p);
+      wave_lds_fence();
+      const uint32_t hits = source_hits(a.n_pops, fa, [&](int q) { return stash[q][lane]; }, live);
+      bool go = __ballot(hits != 0u) != 0ull;
+      if (go) {
+        const int n_ref = a.pop[0].n_ind;
+        uint2 ref = count_piece(rows_of(0), PROBE, r, lane);
+        stash[0][mine] = ref;
+        wave_lds_fence();
+        go = __ballot(ref_may_pass(fa, hits, stash[0][lane].x, n_ref)) != 0ull;
+        if (go) {
+          wave_lds_fence();  // the vote's reads are over before the whole population's counts replace the probe's
+          const uint2 rest = count_piece(rows_of(0) + PROBE * 4, n_ref - PROBE, r, lane);
+          stash[0][mine] = make_uint2(ref.x + rest.x, static_cast<uint32_t>(n_ref) - (ref.y + rest.y));
+          wave_lds_fence();
+          go = __ballot(target_may_matter(a.n_pops, fa, [&](int q) { return stash[q][lane]; }, live)) != 0ull;
+        }
+      }
+      if (!go) {
+        // the row eval_site would have stored: "any" and the sets' conditions all down, no frequency
+        if (lane <= fa.n_sets) __builtin_nontemporal_store(uint64_t{0}, fa.planes + tile * fa.plane_stride + lane);
+        wave_lds_fence();  // the next tile's counts must not overtake the votes' reads
+        continue;
+      }
+      stash[1][mine] = count_pop(1);
+    }
     // SKIP: sources, ref, the vote, then the target (p = 1) -- or nothing
     int k = 0;
-    for (; k < a.n_pops; ++k) {
+    for (; PROBE == 0 && k < a.n_pops; ++k) {
       const int p = !SKIP ? k : k + 2 < a.n_pops ? k + 2 : k + 2 == a.n_pops ? 0 : 1;
       if (SKIP && p == 1) {
         wave_lds_fence();
@@ -160,41 +284,15 @@ __global__ __launch_bounds__(64, MULTI ? 4 : 5) void site_counts_kernel(CountsAr
         reduce_scatter_step<4, 8>(miss32, lane);
         reduce_scatter_step<2, 4>(miss32, lane);
         cnt = make_uint2(sum32[0], static_cast<uint32_t>(n_ind) - miss32[0]);
-      } else {  // n_iter <= kChunkIters + 1: one pass, widened once -- and ONE butterfly for both sums
-        uint32_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0}, ms[4] = {0, 0, 0, 0};
-        accumulate_rows(base, it, n_full, n_full, n_iter, n_ind, r, lo, hi, ms);
-        // a site's alt sum stays below 2^20 and its missing count below 2^12 for the at most 3 984 individuals of this
-        // form, so the two travel through the butterfly in one word: half of the cross-lane work per population, which
-        // is what a tile of NARROW populations is made of (a lone C2: 0.689 against 0.677 of peak; wide populations: the same)
-        static_assert(16 * (kChunkIters + 1) * 255 < (1 << 20) && 16 * (kChunkIters + 1) < (1 << 12), "packed butterfly fields overflow");
-        uint32_t both[16];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          both[4 * j + 0] = lo[j] & 0xFFFFu;
-          both[4 * j + 1] = hi[j] & 0xFFFFu;
-          both[4 * j + 2] = lo[j] >> 16;
-          both[4 * j + 3] = hi[j] >> 16;
-        }
-        if (__ballot((ms[0] | ms[1] | ms[2] | ms[3]) != 0u) != 0ull) {  // wave-uniform: some lane met a missing call
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            both[4 * j + 0] |= (ms[j] & 0xFFu) << 20;
-            both[4 * j + 1] |= ((ms[j] >> 8) & 0xFFu) << 20;
-            both[4 * j + 2] |= ((ms[j] >> 16) & 0xFFu) << 20;
-            both[4 * j + 3] |= (ms[j] >> 24) << 20;
-          }
-        }
-        reduce_scatter_step<16, 32>(both, lane);
-        reduce_scatter_step<8, 16>(both, lane);
-        reduce_scatter_step<4, 8>(both, lane);
-        reduce_scatter_step<2, 4>(both, lane);
-        cnt = make_uint2(both[0] & 0xFFFFFu, static_cast<uint32_t>(n_ind) - (both[0] >> 20));
+      } else {  // n_iter <= kChunkIters + 1: one pass, widened once -- and ONE butterfly for both sums (count_piece)
+        cnt = count_piece(base, n_ind, r, lane);
+        cnt.y = static_cast<uint32_t>(n_ind) - cnt.y;
       }
       const int64_t site = tile * kTile + (lane & 3) * 16 + r;
       if (!SKIP && a.counts && site < a.n_sites) store_counts_nt(a.counts + static_cast<int64_t>(p) * a.n_sites + site, cnt);
       if (FUSED) stash[p][(lane & 3) * 16 + r] = cnt;
     }
-    if (SKIP && k < a.n_pops) {  // the target was left unread
+    if (SKIP && PROBE == 0 && k < a.n_pops) {  // the target was left unread
       wave_lds_fence();  // the next tile's counts must not overtake the vote's reads
       continue;
     }
@@ -218,6 +316,8 @@ int check_plane_stride(int64_t plane_stride, int32_t n_sets) {
 }
 
 extern "C" int32_t sai_skip_min_tgt_ind(void) { return kSkipMinTgtInd; }
+extern "C" int32_t sai_ref_probe_rows(void) { return kRefProbeRows; }
+extern "C" int32_t sai_ref_probe_min_ind(void) { return kRefProbeMinInd; }
 
 extern "C" int64_t sai_plane_words(int64_t n_sites, int32_t n_sets) {
   if (n_sites < 0 || n_sets < 0 || n_sites >= 0x7FFFFFFFll) return -1;
@@ -274,7 +374,6 @@ static int launch_site_counts(sai_ctx* ctx, int64_t n_sites, int32_t n_pops, con
   if (n_sets > 0) fill_eval_sets(fa.es, n_sets, sets_host, n_pops - 2);
   int64_t individuals = 0;
   for (int p = 0; p < n_pops; ++p) individuals += pops[p].n_ind;
-  const dim3 grid(stream_grid(ctx, a.n_tiles, site_pass_waves_per_cu(ctx, a.n_tiles, n_sets, n_pops, individuals)));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // the form that leaves the target unread where no site can pass: only where its outputs are the other form's bit
   // for bit (the candidates' frequencies alone, no counts, no inverted words -- an inverted bit depends on the
@@ -283,8 +382,20 @@ static int launch_site_counts(sai_ctx* ctx, int64_t n_sites, int32_t n_pops, con
   const char* skip_env = std::getenv("SAI_TGT_SKIP");
   const bool skip = n_sets > 0 && !multi && freq_mode == SAI_FREQ_CANDIDATES && !counts && !fa.with_inv &&
                     !fa.es.use_table && pops[1].n_ind >= kSkipMinTgtInd && !(skip_env && skip_env[0] == '0');
+  // ... and ref beyond its first rows: a ref wide enough for that to pay, and fewer sets than the grid rule calls many
+  // (a set-by-set call of many sets has a candidate in nearly every tile: the votes' loops over the sets would be work
+  // for nothing -- 18 of C5's sets: 3.86 against 3.01 ms); SAI_REF_PROBE=0: A/B knob, likewise
+  const char* probe_env = std::getenv("SAI_REF_PROBE");
+  const bool probe = skip && n_sets < many_sets() && pops[0].n_ind >= kRefProbeMinInd && !(probe_env && probe_env[0] == '0');
+  // most tiles of the probing form are 4 KiB behind two trips to memory, not 128 KB of streaming: where the rule
+  // gives wide populations 8 waves per CU -- and only there: the one case the sweep covers -- it takes 24 (C3: 0.541 ms
+  // at 8, 0.413 at 16, 0.396 at 24, 0.403 at 20 and at 32 -- profiles/ref_probe_ab.txt)
+  int waves_per_cu = site_pass_waves_per_cu(ctx, a.n_tiles, n_sets, n_pops, individuals);
+  if (probe && waves_per_cu == 8) waves_per_cu = kRefProbeWavesPerCu;
+  const dim3 grid(stream_grid(ctx, a.n_tiles, waves_per_cu));
   if (n_sets > 0) {
     if (multi) launch_pass(ctx, site_counts_kernel<true, true>, grid, dim3(64), st, a, fa);
+    else if (probe) launch_pass(ctx, site_counts_kernel<false, true, true, kRefProbeRows>, grid, dim3(64), st, a, fa);
     else if (skip) launch_pass(ctx, site_counts_kernel<false, true, true>, grid, dim3(64), st, a, fa);
     else launch_pass(ctx, site_counts_kernel<false, true>, grid, dim3(64), st, a, fa);
   } else {
