@@ -65,6 +65,7 @@ UNITS = [
     "bcf/bcf_decode.hip",
     "bcf/bcf_walk.hip",
     "packed_stats/packed2_freqs.hip",
+    "join/tile_rows.hip",
     *HOST_UNITS,
 ]
 
@@ -223,3 +224,6 @@ def build(force: bool = False, sanitize: bool = False) -> None:
 
     bed_writer.load()
     pgen_writer.load()
+    from sai_amd import site_join_device  # ... and the gathering re-tile's, declared by its own unit (csrc/join/tile_rows.hip)
+
+    site_join_device.load()

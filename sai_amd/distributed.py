@@ -293,11 +293,12 @@ class RowGather:
 
 
 def score_sharded(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_file, output_file: str,
-                  config: str, chunks_per_rank: int = 1) -> Optional[list]:  # fmt: skip
+                  config: str, chunks_per_rank: int = 1, src_file=None) -> Optional[list]:  # fmt: skip
     """``score`` over all ranks of the job: the chromosome's window list is cut into
     ``world * chunks_per_rank`` ChunkGenerator chunks, each rank loads and scores only its own
     regions on its GPU, rank 0 writes the reference's TSV / log files (natively, from the gathered
-    numeric batches) and gets the batches back; the other ranks get None."""
+    numeric batches) and gets the batches back; the other ranks get None.  ``src_file``: every rank reads and
+    joins its own regions of both inputs (``score``); the chunks are the main input's."""
     import torch.distributed as dist
 
     from .generators import ChunkGenerator
@@ -308,7 +309,8 @@ def score_sharded(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc
     require_polarised_input(cfg.statistics, anc_allele_file)
     generator = ChunkGenerator(vcf_file=vcf_file, chr_name=chr_name, window_size=win_len, step_size=win_step,
                                num_chunks=max(world * chunks_per_rank, 1))  # fmt: skip
-    preprocessor = chunk_preprocessor_for(cfg, vcf_file, win_len, win_step, output_file, anc_allele_file)
+    second = {} if src_file is None else {"src_file": src_file}
+    preprocessor = chunk_preprocessor_for(cfg, vcf_file, win_len, win_step, output_file, anc_allele_file, **second)
     if rank == 0:
         write_headers(output_file, cfg.statistics, cfg.ploidies)
     if world > 1:

@@ -10,6 +10,15 @@ from ..sai import score
 from .argument_validation import existed_eigenstrat, existed_file, existed_fileset, existed_pfile, positive_int
 
 
+def existed_input(value: str) -> str:
+    """``--src-input``: a file, or ``PREFIX.bed`` / ``PREFIX.geno`` / ``PREFIX.pgen`` of a fileset whose files exist."""
+    checks = {".bed": existed_fileset, ".geno": existed_eigenstrat, ".pgen": existed_pfile}
+    for suffix, check in checks.items():
+        if value.endswith(suffix):
+            return check(value[: -len(suffix)]) + suffix
+    return existed_file(value)
+
+
 def resolve_workers(args: argparse.Namespace) -> int:
     """``--num-workers``, else $SAI_AMD_GPUS, else 1 (the reference's CLI, score_parser.py:64).  The environment is
     read when `score` runs, not while the parser is built: a malformed value is `sai score`'s usage error only,
@@ -53,6 +62,7 @@ def _run_score(args: argparse.Namespace) -> None:
         config=args.config,
         num_workers=args.num_workers,
         layout=args.layout,
+        **({} if args.src_input is None else {"src_file": args.src_input}),
     )
 
 
@@ -98,4 +108,10 @@ def add_score_parser(subparsers) -> None:
                         "(two bits per call, decoded straight from a PLINK 1 fileset given with --bfile or a PLINK 2 fileset given "
                         "with --pfile; U, Q, fd, df, Danc and Dplus, not DD; one worker; with --anc-alleles a missing call in a row "
                         "flipped by the ancestral allele does not fit two bits and asks for int8). Default: $SAI_AMD_LAYOUT, else int8.")  # fmt: skip
+    # not a flag of the reference: the archaic sources in a file of their own
+    parser.add_argument("--src-input", dest="src_input", type=existed_input, default=None, metavar="PATH",
+                        help="Read the samples of the configuration's src list from this file instead of the main input, and score "
+                        "the sites both files hold: anything --vcf takes (a plain, gzip or bgzip VCF, a BCF), or PREFIX.bed, "
+                        "PREFIX.geno or PREFIX.pgen of a fileset. Requires --anc-alleles (the two inputs are reconciled through "
+                        "the ancestral allele) and the int8 layout; the windows come from the main input. Default: None.")  # fmt: skip
     parser.set_defaults(runner=_run_score, score_parser=parser)

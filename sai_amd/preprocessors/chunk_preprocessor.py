@@ -28,7 +28,11 @@ class ChunkPreprocessor(DataPreprocessor):
         anc_allele_file: str = None,
         num_src: int = 1,
         layout: str = "int8",
+        src_file: str = None,
     ):
+        # the samples of the ``src`` group come from this file, joined to the others' sites (sai_amd.site_join); the window
+        # grid stays the main input's
+        self.src_file = src_file
         self.layout = layout  # "packed2": a PLINK 1 or PLINK 2 fileset decoded straight into the 2-bit layout (every statistic but DD)
         self.vcf_file = vcf_file
         self.ref_ind_file = ref_ind_file
@@ -63,7 +67,7 @@ class ChunkPreprocessor(DataPreprocessor):
         results, pos_dev = read_data_device(
             Engine.get(), vcf_file=self.vcf_file, chr_name=chr_name, start=None, end=None, ref_ind_file=self.ref_ind_file,
             tgt_ind_file=self.tgt_ind_file, src_ind_file=self.src_ind_file, out_ind_file=self.out_ind_file,
-            ploidy_config=self.ploidy_config, anc_allele_file=self.anc_allele_file)  # fmt: skip
+            ploidy_config=self.ploidy_config, anc_allele_file=self.anc_allele_file, **self._second_input())  # fmt: skip
         span = None
         for data, _ in (results.get(g, (None, None)) for g in ("ref", "tgt", "src", "outgroup")):
             for block in (data or {}).values():
@@ -82,8 +86,27 @@ class ChunkPreprocessor(DataPreprocessor):
         computes and sends to rank 0, where ``unpack_results`` turns the batches into items."""
         return self.feature_preprocessor.score_windows(self._window_generator(chr_name, start, end, preloaded))
 
+    def _second_input(self) -> dict:
+        """``src_file=`` for the readers that take it; nothing without a second input, whose calls stay what they were."""
+        return {} if self.src_file is None else {"src_file": self.src_file}
+
     def _window_generator(self, chr_name: str, start: int, end: int, preloaded=None):
+        resident = os.environ.get("SAI_AMD_INGEST", "device") != "host"
+        second = self._second_input()
+        if second and resident:
+            # the generator joins host matrices only: on the resident route the two inputs are read and joined here
+            # (read_data_device) and handed over as one preloaded result
+            if preloaded is None:
+                from ..engine import Engine
+                from ..utils.read_data import read_data_device
+
+                preloaded = read_data_device(
+                    Engine.get(), vcf_file=self.vcf_file, chr_name=chr_name, start=start, end=end, ref_ind_file=self.ref_ind_file,
+                    tgt_ind_file=self.tgt_ind_file, src_ind_file=self.src_ind_file, out_ind_file=self.out_ind_file,
+                    ploidy_config=self.ploidy_config, anc_allele_file=self.anc_allele_file, layout=self.layout, **second)  # fmt: skip
+            second = {}
         return WindowGenerator(
+            **second,
             preloaded=preloaded,
             vcf_file=self.vcf_file,
             chr_name=chr_name,
@@ -98,7 +121,7 @@ class ChunkPreprocessor(DataPreprocessor):
             ploidy_config=self.ploidy_config,
             anc_allele_file=self.anc_allele_file,
             num_src=self.num_src,
-            resident=os.environ.get("SAI_AMD_INGEST", "device") != "host",
+            resident=resident,
             layout=self.layout,
         )
 

@@ -70,12 +70,14 @@ def require_polarised_input(stat_config, anc_allele_file) -> None:
 
 
 def chunk_preprocessor_for(cfg: GlobalConfig, vcf_file, win_len, win_step, output_file, anc_allele_file,
-                           layout: str = "int8") -> ChunkPreprocessor:
+                           layout: str = "int8", src_file=None) -> ChunkPreprocessor:
     """The chunk driver of a run: the sample lists come from the configuration's ``populations``
-    section (sai.py:95-107).  Shared by ``score`` and ``sai_amd.distributed.score_sharded``."""
+    section (sai.py:95-107).  Shared by ``score`` and ``sai_amd.distributed.score_sharded``.  ``src_file``: the
+    samples of the ``src`` list are read from that file (``require_second_input``)."""
     files = {group: cfg.populations.get_population(group) for group in ("ref", "tgt", "src", "outgroup")}
+    second = {} if src_file is None else {"src_file": src_file}
     return ChunkPreprocessor(vcf_file, files["ref"], files["tgt"], files["src"], files["outgroup"], win_len, win_step,
-                             output_file, cfg.ploidies, cfg.statistics, anc_allele_file=anc_allele_file, layout=layout)  # fmt: skip
+                             output_file, cfg.ploidies, cfg.statistics, anc_allele_file=anc_allele_file, layout=layout, **second)  # fmt: skip
 
 
 LAYOUTS = ("int8", "packed2")
@@ -109,6 +111,20 @@ def require_packed2_input(vcf_file, config: str, num_workers: int) -> None:
     other = [name for name, value in stats.items() if name not in ("U", "Q", *_POLARISED) and value is not False]
     if other:
         raise ValueError(f"layout 'packed2' serves the U and Q statistics only, but {other[0]} is configured.")
+
+
+def require_second_input(vcf_file, src_file, anc_allele_file, layout: str) -> None:
+    """What ``score(..., src_file=)`` cannot serve is refused here, before anything is read or written: two inputs are
+    reconciled through the ancestral allele (``site_join.require_second_input``, whose sentence this raises), they are
+    read in the int8 layout, and the file has to exist as the main input has to."""
+    from . import site_join
+    from .utils.filesets import is_fileset
+
+    site_join.require_second_input(src_file, anc_allele_file)
+    if layout == "packed2":
+        raise ValueError("a source file of its own is read in the int8 layout: `src_file` cannot be combined with layout 'packed2'.")
+    if not is_fileset(src_file) and not os.path.exists(src_file):
+        raise ValueError(f"cannot open VCF {src_file}")  # the words a missing main input is refused with
 
 
 def _reads_in_one_pass(vcf_file: str) -> bool:
@@ -175,7 +191,7 @@ def _scan_while_reading(driver: ChunkPreprocessor, vcf_file: str, chr_name: str)
     return span, preloaded
 
 
-def chunks_for_memory(vcf_file: str, layout: str = "int8") -> int:
+def chunks_for_memory(vcf_file: str, layout: str = "int8", src_file=None) -> int:
     """How many ChunkGenerator chunks a one-process `score` cuts the chromosome into so that a chunk's genotypes
     fit the GPU: 1 (the reference's one-process form, sai.py:86-93 with one worker) unless the file promises more
     int8 genotype bytes than the budget -- then ceil(bytes / budget), the grain the sharded route already uses
@@ -185,7 +201,8 @@ def chunks_for_memory(vcf_file: str, layout: str = "int8") -> int:
     copy per population, hence a budget of a quarter of the free HBM.  ``SAI_AMD_HBM_BUDGET_BYTES`` overrides it.
     A PLINK ``.bed`` and a packed ``.geno`` hold four genotypes per byte: 4 x their size stays resident; a text
     ``.geno`` holds one: 1 x.  With ``layout="packed2"`` a ``.bed`` is never widened: 1 x its size stays resident; a
-    ``.pgen`` is compressed, so its header's counts say it: variant_ct x ceil(sample_ct / 4)."""
+    ``.pgen`` is compressed, so its header's counts say it: variant_ct x ceil(sample_ct / 4).  ``src_file`` (int8 layout): the
+    source file's own estimate is added to the main input's -- both blocks are resident while they are joined."""
     from .utils.filesets import resident_bytes
 
     try:
@@ -202,6 +219,12 @@ def chunks_for_memory(vcf_file: str, layout: str = "int8") -> int:
         if resident is None:
             size = os.path.getsize(vcf_file)
             resident = size * 3 if str(vcf_file).endswith((".gz", ".bgz")) else size // 4
+        if src_file is not None:
+            second = resident_bytes(src_file)
+            if second is None:
+                size = os.path.getsize(src_file)
+                second = size * 3 if str(src_file).endswith((".gz", ".bgz")) else size // 4
+            resident += second
     except OSError:
         return 1
     raw = os.environ.get("SAI_AMD_HBM_BUDGET_BYTES", "")
@@ -221,30 +244,33 @@ def chunks_for_memory(vcf_file: str, layout: str = "int8") -> int:
     return max(1, -(-resident // max(budget, 1)))
 
 
-def _score_over_ranks(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config) -> None:
+def _score_over_ranks(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config, src_file=None) -> None:
     """This process is one rank of a launched job: take the sharded route and leave the group cleanly."""
     from .distributed import score_sharded, shutdown_process_group
     from .launcher import chunks_per_worker
 
+    second = {} if src_file is None else {"src_file": src_file}
     try:
         score_sharded(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config,
-                      chunks_per_rank=chunks_per_worker())  # fmt: skip
+                      chunks_per_rank=chunks_per_worker(), **second)  # fmt: skip
     finally:
         shutdown_process_group()
 
 
-def _score_cli_arguments(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config, num_workers) -> list:
+def _score_cli_arguments(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config, num_workers, src_file=None) -> list:
     from .utils.filesets import cli_source
 
     argv = ["score", *cli_source(vcf_file), "--chr-name", chr_name, "--win-len", win_len, "--win-step", win_step,
             "--output", output_file, "--config", config, "--num-workers", num_workers]  # fmt: skip
     if anc_allele_file is not None:
         argv += ["--anc-alleles", anc_allele_file]
+    if src_file is not None:
+        argv += ["--src-input", src_file]
     return [str(a) for a in argv]
 
 
 def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_file: str, output_file: str, config: str,
-          num_workers: int, layout: str = None) -> None:  # fmt: skip
+          num_workers: int, layout: str = None, *, src_file: str = None) -> None:  # fmt: skip
     """Sliding-window scores of one chromosome, written as the reference writes them (TSV +
     ``.U.log`` + ``.Q.log``; interface of sai.py:33-42).
 
@@ -261,17 +287,29 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
     per chunk, the same files byte for byte.  What that route cannot serve (DD among the statistics) is a ValueError
     before anything is read (``require_packed2_input``); a missing call in a row flipped by the ancestral allele (dosage 4
     at ploidy 2) is one while reading: with ``anc_allele_file`` -- which fd, df, Danc and Dplus require -- the layout serves
-    panels without a missing call in a flipped row, and the message names the int8 layout for the others."""
+    panels without a missing call in a flipped row, and the message names the int8 layout for the others.
+
+    ``src_file``: the samples of the configuration's ``src`` list are read from this file -- anything ``vcf_file`` may be:
+    a plain, gzip or bgzip VCF, a BCF, ``PREFIX.bed`` / ``.geno`` / ``.pgen`` -- and those of the other lists from
+    ``vcf_file``; both are polarised by ``anc_allele_file``, which is required, and scored over the sites both readers kept
+    (``sai_amd.site_join``), in the int8 layout.  THE WINDOW GRID IS THE MAIN INPUT'S: ``ChunkGenerator`` and the one-pass
+    scan read ``vcf_file`` as before; the source file contributes genotypes, not windows.  What cannot be served is
+    refused before the output directory is made (``require_second_input``)."""
     from . import launcher
 
     num_workers = 1 if num_workers is None else int(num_workers)
     if num_workers < 1:
         raise ValueError("`num_workers` must be a positive integer.")
     layout = resolve_layout(layout)
+    second = {}
+    if src_file is not None:
+        src_file = str(src_file)
+        require_second_input(vcf_file, src_file, anc_allele_file, layout)
+        second = {"src_file": src_file}
     if layout == "packed2":
         require_packed2_input(vcf_file, config, num_workers)
     if launcher.in_rank_job():
-        _score_over_ranks(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config)
+        _score_over_ranks(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config, **second)
         return
     if num_workers > 1:
         # the errors a one-process run raises before any work (configuration, polarisation) are raised here,
@@ -279,16 +317,16 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
         cfg = load_config(config)
         require_polarised_input(cfg.statistics, anc_allele_file)
         rc = launcher.launch_ranks(
-            num_workers, _score_cli_arguments(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config, num_workers),
+            num_workers, _score_cli_arguments(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config, num_workers, **second),
             module="sai_amd", who="sai score")  # fmt: skip
         if rc != 0:
             raise launcher.RankJobFailed(num_workers, rc)
         return
     cfg = load_config(config)
     require_polarised_input(cfg.statistics, anc_allele_file)
-    driver = chunk_preprocessor_for(cfg, vcf_file, win_len, win_step, output_file, anc_allele_file, layout=layout)
+    driver = chunk_preprocessor_for(cfg, vcf_file, win_len, win_step, output_file, anc_allele_file, layout=layout, **second)
     span, preloaded = None, None
-    n_chunks = chunks_for_memory(vcf_file, layout)  # 1 unless the chromosome's genotypes would not fit the GPU at once
+    n_chunks = chunks_for_memory(vcf_file, layout, **second)  # 1 unless the chromosome's genotypes would not fit the GPU at once
     if n_chunks == 1 and _reads_in_one_pass(vcf_file):
         span, preloaded = _scan_while_reading(driver, vcf_file, str(chr_name))
     chunks = ChunkGenerator(vcf_file=vcf_file, chr_name=chr_name, window_size=win_len, step_size=win_step,

@@ -2,8 +2,12 @@
 from a file of their own").  The panel (ref, tgt, outgroup) and the source file are each read by their own reader, both
 polarised by the same ancestral alleles; here their position lists are brought to the common rows
 (``sai_site_join_host``) and every population keeps the rows of the common sites only, so that everything downstream sees
-one position list.  This version serves the host readers only (``read_dosage_data(..., src_file=)`` and the
-``WindowGenerator`` over host matrices): numpy row selection; ``score`` does not take a second input yet.
+one position list.  The join itself is a host call for every route: the readers hand their positions back as host
+arrays and the window grid needs the common positions there.  What differs is how the rows are applied: the host
+readers (``read_dosage_data(..., src_file=)``, the ``WindowGenerator`` over host matrices) select them with numpy here;
+the resident reader (``read_data_device(..., src_file=)``, which ``score(..., src_file=)`` and ``sai score --src-input``
+run on) uploads each input's row list once and re-tiles every population from those rows of its device block in one
+launch (``sai_amd.site_join_device``).
 """
 
 from __future__ import annotations

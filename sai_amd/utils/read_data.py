@@ -206,7 +206,8 @@ def _assemble(samples_by_group, ploidy_config, block) -> dict:
 
 
 def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file,
-                     out_ind_file=None, anc_allele_file=None, start: int = None, end: int = None, layout: str = "int8"):
+                     out_ind_file=None, anc_allele_file=None, start: int = None, end: int = None, layout: str = "int8", *,
+                     src_file: Optional[str] = None):
     """``read_data`` with the genotypes left in HBM: one streaming pass over the file (text over PCIe,
     tokenised on the GPU, ``device_vcf.load_dosage_device``) for all populations and ploidies, then one
     re-tiling launch per population straight from the shared [record][sample] block.  Returns
@@ -218,17 +219,60 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
 
     ``layout="packed2"`` (a PLINK 1 or a PLINK 2 fileset): every ``GT`` is a ``PackedPop``, decoded from the ``.bed``
     rows or the ``.pgen`` records straight into the 2-bit layout (the reader's ``load_packed_device``); no int8 block
-    is built on the way."""
+    is built on the way.
+
+    ``src_file`` (int8 layout): the samples of the ``src`` group are read from that file, those of the other groups from
+    ``vcf_file``, each by its own reader with the same region and ancestral alleles; the positions are joined on the host
+    (``site_join.join_host``) and every population of both inputs is tiled from the rows of the common sites by one
+    launch that gathers while it re-tiles (``site_join_device.RowTiler``).  All blocks share one ``POS``, the common
+    positions, and the result carries ``"site_join"``, as ``read_dosage_data(..., src_file=)``'s does."""
     import torch
 
     from .filesets import reader_for
 
+    if src_file is not None:
+        from ..site_join import require_second_input
+
+        require_second_input(src_file, anc_allele_file)
+        if layout == "packed2":
+            raise ValueError("a source file of its own is read in the int8 layout: `src_file` cannot be combined with layout 'packed2'.")
+        if layout != "int8":
+            raise ValueError("layout must be 'int8' or 'packed2'")
+        return _read_joined_device(eng, vcf_file, src_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
+                                   anc_allele_file, start, end)  # fmt: skip
     reader = reader_for(vcf_file)
     if layout == "packed2":
         return _read_packed_device(eng, reader, vcf_file, str(chr_name), ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file,
                                    out_ind_file, anc_allele_file, start, end)  # fmt: skip
     if layout != "int8":
         raise ValueError("layout must be 'int8' or 'packed2'")
+    samples_by_group, column, blocks, pos, n_matched = _read_blocks_device(eng, reader, vcf_file, chr_name, ploidy_config, ref_ind_file,
+                                                                          tgt_ind_file, src_ind_file, out_ind_file, anc_allele_file,
+                                                                          start, end)  # fmt: skip
+    if column is None:
+        return {"outgroup": (None, None), **{group: (None, samples) for group, samples in samples_by_group.items()}}, None
+
+    def block(population, pop_names, ploidy):
+        if n_matched == 0:
+            return None
+        where_cols = [column[(nme, ploidy)] for nme in pop_names]
+        used = {k for k, _ in where_cols}
+        if len(used) == 1:
+            tiled = eng.tile_columns(blocks[used.pop()], [c for _, c in where_cols])
+        else:  # the population's samples were tokenised in different passes: gather its columns first
+            tiled = eng._tile_device(torch.stack([blocks[k][:, c] for k, c in where_cols], dim=1).contiguous())
+        return ChromosomeData(POS=pos, REF=None, ALT=None, GT=tiled)
+
+    pos_dev = torch.from_numpy(pos).to(eng.device) if n_matched else None
+    return _assemble(samples_by_group, ploidy_config, block), pos_dev
+
+
+def _read_blocks_device(eng, reader, vcf_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
+                        anc_allele_file, start, end):
+    """What ``read_data_device`` has before it tiles: ``(samples_by_group, column, blocks, pos, n_matched)`` -- the
+    samples of every group, (sample, ploidy) -> (pass, column of the pass's block), the int8 [record][sample] device
+    block of every pass, the positions the reader kept and the records it met.  ``column`` is None (and nothing was
+    read) when no population with a ploidy entry names a sample."""
     fileset = reader is not None
     if fileset:
         load_dosage_device = reader.load_dosage_device
@@ -252,7 +296,7 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
                 passes[k]["ploidies"].append(ploidy)
                 passes[k]["seen"].add(nme)
     if not passes:
-        return {"outgroup": (None, None), **{group: (None, samples) for group, samples in samples_by_group.items()}}, None
+        return samples_by_group, None, [], None, 0
     where = chr_name if start is None and end is None else f"{chr_name}:{start}-{end}"
     if not fileset and not os.path.exists(vcf_file):
         raise ValueError(f"Failed to read VCF file {vcf_file} from {where}: cannot open VCF {vcf_file}")
@@ -267,20 +311,67 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
     except Exception as e:  # utils.py:139-140
         raise ValueError(f"Failed to read VCF file {vcf_file} from {where}: {e}") from e
     _check_anc_found(anc_allele_file, n_matched, n_anc, chr_name, start, end)
+    return samples_by_group, column, blocks, pos, n_matched
 
-    def block(population, pop_names, ploidy):
-        if n_matched == 0:
-            return None
-        where_cols = [column[(nme, ploidy)] for nme in pop_names]
-        used = {k for k, _ in where_cols}
-        if len(used) == 1:
-            tiled = eng.tile_columns(blocks[used.pop()], [c for _, c in where_cols])
-        else:  # the population's samples were tokenised in different passes: gather its columns first
-            tiled = eng._tile_device(torch.stack([blocks[k][:, c] for k, c in where_cols], dim=1).contiguous())
-        return ChromosomeData(POS=pos, REF=None, ALT=None, GT=tiled)
 
-    pos_dev = torch.from_numpy(pos).to(eng.device) if n_matched else None
-    return _assemble(samples_by_group, ploidy_config, block), pos_dev
+def _read_joined_device(eng, vcf_file, src_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
+                        anc_allele_file, start, end):
+    """``read_data_device(..., src_file=)``: the panel's blocks and the source file's, each read as a one-input call
+    reads them, then the host join of their positions and one gathering re-tile per population."""
+    import torch
+
+    from .. import site_join
+    from ..site_join_device import RowTiler, upload_rows
+    from .filesets import reader_for
+
+    sides = [_read_blocks_device(eng, reader_for(f), f, chr_name, ploidy_config, *lists, anc_allele_file, start, end)
+             for f, lists in ((vcf_file, (ref_ind_file, tgt_ind_file, None, out_ind_file)), (src_file, (None, None, src_ind_file, None)))]  # fmt: skip
+
+    def merged(block_of_side):
+        """ref, tgt and outgroup of the panel and src of the source file as one result (``site_join._merged``)."""
+        out = {}
+        for side, (samples_by_group, *_), block in zip((0, 1), sides, block_of_side):
+            got = _assemble(samples_by_group, ploidy_config, block)
+            for group in site_join.GROUPS:
+                if (group == "src") == (side == 1):
+                    out[group] = got.get(group, (None, None))
+        return out
+
+    no_data = lambda population, pop_names, ploidy: None  # noqa: E731
+    if any(column is None or n_matched == 0 for _, column, _, _, n_matched in sides):  # a region without a record in one of the inputs
+        return merged((no_data, no_data)), None
+    pos_a, pos_b = sides[0][3], sides[1][3]
+    rows_a, rows_b, info = site_join.join_host(pos_a, pos_b)
+    site_join._check_info(info, pos_a, pos_b, vcf_file, src_file)
+    summary = site_join._summary(info, pos_a.size, pos_b.size, vcf_file, src_file)
+    if summary["n_common"] == 0:
+        out = merged((no_data, no_data))
+        out["site_join"] = summary
+        return out, None
+    pos = np.ascontiguousarray(pos_a).copy() if summary["panel_identity"] else np.ascontiguousarray(pos_a[rows_a])
+    tiler = RowTiler(eng)
+
+    def tiling(side, identity, rows):
+        _, column, blocks, _, _ = sides[side]
+        rows_dev = None if identity else upload_rows(eng, rows)  # one upload per input; the identity passes no list
+
+        def block(population, pop_names, ploidy):
+            where_cols = [column[(nme, ploidy)] for nme in pop_names]
+            used, cols = {k for k, _ in where_cols}, [c for _, c in where_cols]
+            if len(used) == 1 and cols == list(range(cols[0], cols[0] + len(cols))):  # the usual case: one run of columns
+                source, col0 = blocks[used.pop()], cols[0]
+            elif cols:  # gathered by columns first, as the one-input read does
+                source, col0 = torch.stack([blocks[k][:, c] for k, c in where_cols], dim=1).contiguous(), 0
+            else:
+                source, col0 = blocks[0][:, :0], 0
+            return ChromosomeData(POS=pos, REF=None, ALT=None, GT=tiler.tile(source, col0, len(cols), rows_dev))
+
+        return block
+
+    out = merged((tiling(0, summary["panel_identity"], rows_a), tiling(1, summary["source_identity"], rows_b)))
+    tiler.check()
+    out["site_join"] = summary
+    return out, torch.from_numpy(pos).to(eng.device)
 
 
 def _read_packed_device(eng, reader, vcf_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
