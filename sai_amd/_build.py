@@ -39,6 +39,7 @@ HOST_UNITS = [
     "bcf/csi_index.cpp",
     "packed_stats/packed2_freqs_host.cpp",
     "join/site_join_host.cpp",
+    "join/site_join_many_host.cpp",
 ]
 UNITS = [
     "core.hip",
@@ -65,6 +66,7 @@ UNITS = [
     "bcf/bcf_decode.hip",
     "bcf/bcf_walk.hip",
     "packed_stats/packed2_freqs.hip",
+    "join/tile_parts.hip",
     "join/tile_rows.hip",
     *HOST_UNITS,
 ]
@@ -227,3 +229,7 @@ def build(force: bool = False, sanitize: bool = False) -> None:
     from sai_amd import site_join_device  # ... and the gathering re-tile's, declared by its own unit (csrc/join/tile_rows.hip)
 
     site_join_device.load()
+    from sai_amd import site_join_many, site_join_parts  # ... and those of several source files: the k-way join and the re-tile from parts
+
+    site_join_many.load()
+    site_join_parts.load()

@@ -298,7 +298,8 @@ def score_sharded(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc
     ``world * chunks_per_rank`` ChunkGenerator chunks, each rank loads and scores only its own
     regions on its GPU, rank 0 writes the reference's TSV / log files (natively, from the gathered
     numeric batches) and gets the batches back; the other ranks get None.  ``src_file``: every rank reads and
-    joins its own regions of both inputs (``score``); the chunks are the main input's."""
+    joins its own regions of both inputs (``score``), or of all of them where it is a list of source files; the chunks are
+    the main input's."""
     import torch.distributed as dist
 
     from .generators import ChunkGenerator

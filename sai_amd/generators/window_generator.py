@@ -71,7 +71,8 @@ class WindowGenerator(DataGenerator):
         ``preloaded`` = what ``read_data_device`` returned for exactly this region (the caller read it
         before it knew the chunk bounds, ChunkPreprocessor.preload).  ``layout="packed2"`` (with ``resident``): the
         populations are read as ``PackedPop`` blocks (``read_data_device``).  ``src_file``: the samples of the ``src``
-        group are read from that file and joined to the others' sites (``sai_amd.site_join``); host matrices only."""
+        group are read from that file -- or, a list or tuple of 2 to 16 paths, each from the one file that holds it
+        (``sai_amd.site_join_many``) -- and joined to the others' sites (``sai_amd.site_join``); host matrices only."""
         if win_len <= 0:
             raise ValueError("`win_len` must be greater than 0.")
         if win_step < 0:

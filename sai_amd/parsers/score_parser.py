@@ -19,6 +19,15 @@ def existed_input(value: str) -> str:
     return existed_file(value)
 
 
+class SourceInput(argparse.Action):
+    """``--src-input PATH``, which may be repeated: the first occurrence leaves the ``str`` (the namespace of one source
+    file is what it was), a further one turns the value into the list of all paths in command-line order."""
+
+    def __call__(self, parser, namespace, value, option_string=None):
+        have = getattr(namespace, self.dest, None)
+        setattr(namespace, self.dest, value if have is None else [*have, value] if isinstance(have, list) else [have, value])
+
+
 def resolve_workers(args: argparse.Namespace) -> int:
     """``--num-workers``, else $SAI_AMD_GPUS, else 1 (the reference's CLI, score_parser.py:64).  The environment is
     read when `score` runs, not while the parser is built: a malformed value is `sai score`'s usage error only,
@@ -109,9 +118,10 @@ def add_score_parser(subparsers) -> None:
                         "with --pfile; U, Q, fd, df, Danc and Dplus, not DD; one worker; with --anc-alleles a missing call in a row "
                         "flipped by the ancestral allele does not fit two bits and asks for int8). Default: $SAI_AMD_LAYOUT, else int8.")  # fmt: skip
     # not a flag of the reference: the archaic sources in a file of their own
-    parser.add_argument("--src-input", dest="src_input", type=existed_input, default=None, metavar="PATH",
+    parser.add_argument("--src-input", dest="src_input", type=existed_input, action=SourceInput, default=None, metavar="PATH",
                         help="Read the samples of the configuration's src list from this file instead of the main input, and score "
                         "the sites both files hold: anything --vcf takes (a plain, gzip or bgzip VCF, a BCF), or PREFIX.bed, "
                         "PREFIX.geno or PREFIX.pgen of a fileset. Requires --anc-alleles (the two inputs are reconciled through "
-                        "the ancestral allele) and the int8 layout; the windows come from the main input. Default: None.")  # fmt: skip
+                        "the ancestral allele) and the int8 layout; the windows come from the main input. May be given up to 16 times, once "
+                        "per source file: every src sample must then be held by exactly one of the files. Default: None.")  # fmt: skip
     parser.set_defaults(runner=_run_score, score_parser=parser)

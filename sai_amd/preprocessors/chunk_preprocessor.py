@@ -30,7 +30,8 @@ class ChunkPreprocessor(DataPreprocessor):
         layout: str = "int8",
         src_file: str = None,
     ):
-        # the samples of the ``src`` group come from this file, joined to the others' sites (sai_amd.site_join); the window
+        # the samples of the ``src`` group come from this file (a list or tuple: from these files), joined to the others'
+        # sites (sai_amd.site_join, sai_amd.site_join_many); the window
         # grid stays the main input's
         self.src_file = src_file
         self.layout = layout  # "packed2": a PLINK 1 or PLINK 2 fileset decoded straight into the 2-bit layout (every statistic but DD)

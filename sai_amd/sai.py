@@ -120,11 +120,15 @@ def require_second_input(vcf_file, src_file, anc_allele_file, layout: str) -> No
     from . import site_join
     from .utils.filesets import is_fileset
 
-    site_join.require_second_input(src_file, anc_allele_file)
+    from .site_join_many import as_list
+
+    files = as_list(src_file)  # one path, or the 2 to 16 of several source files: every refusal applies to every file
+    site_join.require_second_input(files[0], anc_allele_file)
     if layout == "packed2":
         raise ValueError("a source file of its own is read in the int8 layout: `src_file` cannot be combined with layout 'packed2'.")
-    if not is_fileset(src_file) and not os.path.exists(src_file):
-        raise ValueError(f"cannot open VCF {src_file}")  # the words a missing main input is refused with
+    for f in files:
+        if not is_fileset(f) and not os.path.exists(f):
+            raise ValueError(f"cannot open VCF {f}")  # the words a missing main input is refused with
 
 
 def _reads_in_one_pass(vcf_file: str) -> bool:
@@ -202,7 +206,9 @@ def chunks_for_memory(vcf_file: str, layout: str = "int8", src_file=None) -> int
     A PLINK ``.bed`` and a packed ``.geno`` hold four genotypes per byte: 4 x their size stays resident; a text
     ``.geno`` holds one: 1 x.  With ``layout="packed2"`` a ``.bed`` is never widened: 1 x its size stays resident; a
     ``.pgen`` is compressed, so its header's counts say it: variant_ct x ceil(sample_ct / 4).  ``src_file`` (int8 layout): the
-    source file's own estimate is added to the main input's -- both blocks are resident while they are joined."""
+    source file's own estimate is added to the main input's -- both blocks are resident while they are joined; with several
+    source files (a list or tuple), every file's."""
+    from .site_join_many import as_list
     from .utils.filesets import resident_bytes
 
     try:
@@ -219,11 +225,11 @@ def chunks_for_memory(vcf_file: str, layout: str = "int8", src_file=None) -> int
         if resident is None:
             size = os.path.getsize(vcf_file)
             resident = size * 3 if str(vcf_file).endswith((".gz", ".bgz")) else size // 4
-        if src_file is not None:
-            second = resident_bytes(src_file)
+        for f in as_list(src_file):
+            second = resident_bytes(f)
             if second is None:
-                size = os.path.getsize(src_file)
-                second = size * 3 if str(src_file).endswith((".gz", ".bgz")) else size // 4
+                size = os.path.getsize(f)
+                second = size * 3 if str(f).endswith((".gz", ".bgz")) else size // 4
             resident += second
     except OSError:
         return 1
@@ -258,14 +264,15 @@ def _score_over_ranks(vcf_file, chr_name, win_len, win_step, anc_allele_file, ou
 
 
 def _score_cli_arguments(vcf_file, chr_name, win_len, win_step, anc_allele_file, output_file, config, num_workers, src_file=None) -> list:
+    from .site_join_many import as_list
     from .utils.filesets import cli_source
 
     argv = ["score", *cli_source(vcf_file), "--chr-name", chr_name, "--win-len", win_len, "--win-step", win_step,
             "--output", output_file, "--config", config, "--num-workers", num_workers]  # fmt: skip
     if anc_allele_file is not None:
         argv += ["--anc-alleles", anc_allele_file]
-    if src_file is not None:
-        argv += ["--src-input", src_file]
+    for f in as_list(src_file):
+        argv += ["--src-input", f]  # once per source file
     return [str(a) for a in argv]
 
 
@@ -294,7 +301,10 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
     ``vcf_file``; both are polarised by ``anc_allele_file``, which is required, and scored over the sites both readers kept
     (``sai_amd.site_join``), in the int8 layout.  THE WINDOW GRID IS THE MAIN INPUT'S: ``ChunkGenerator`` and the one-pass
     scan read ``vcf_file`` as before; the source file contributes genotypes, not windows.  What cannot be served is
-    refused before the output directory is made (``require_second_input``)."""
+    refused before the output directory is made (``require_second_input``).  A list or tuple of 2 to 16 paths (a sequence of
+    one is that path): one file per archaic individual or per lab; every sample of the ``src`` list must be held by exactly
+    one of the files and every file must hold one, the sites are those ALL inputs hold, and the individuals of a population
+    stand in the order of the ``src`` list (``sai_amd.site_join_many``)."""
     from . import launcher
 
     num_workers = 1 if num_workers is None else int(num_workers)
@@ -303,8 +313,13 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
     layout = resolve_layout(layout)
     second = {}
     if src_file is not None:
-        src_file = str(src_file)
+        from .site_join_many import is_many, require_sources, source_files
+
+        src_file = source_files(src_file)  # the str of one file, or the list of several
         require_second_input(vcf_file, src_file, anc_allele_file, layout)
+        if is_many(src_file):  # which sample comes from which file: every src sample from exactly one, every file holding one
+            cfg = load_config(config)
+            require_sources(src_file, cfg.ploidies, cfg.populations.get_population("src"))
         second = {"src_file": src_file}
     if layout == "packed2":
         require_packed2_input(vcf_file, config, num_workers)

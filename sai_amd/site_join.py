@@ -7,7 +7,8 @@ arrays and the window grid needs the common positions there.  What differs is ho
 readers (``read_dosage_data(..., src_file=)``, the ``WindowGenerator`` over host matrices) select them with numpy here;
 the resident reader (``read_data_device(..., src_file=)``, which ``score(..., src_file=)`` and ``sai score --src-input``
 run on) uploads each input's row list once and re-tiles every population from those rows of its device block in one
-launch (``sai_amd.site_join_device``).
+launch (``sai_amd.site_join_device``).  Several source files -- a list in place of the one path -- are
+``sai_amd.site_join_many``, which builds on this module.
 """
 
 from __future__ import annotations

@@ -67,6 +67,45 @@ def resident_bytes(path) -> Optional[int]:
     return size * 4
 
 
+def _chrom_line_samples(path, lines) -> list:
+    for line in lines:
+        if line.startswith("#CHROM"):
+            return line.rstrip("\r\n").split("\t")[9:]
+        if not line.startswith("#"):
+            break
+    raise ValueError(f"{path}: no #CHROM header line")
+
+
+def input_samples(path) -> list:
+    """The sample names an input holds, in its order, for anything the readers take: the ``#CHROM`` line of a plain,
+    gzip or bgzip VCF or of a BCF's header text, the second column (IID) of a ``.fam``, the first of an ``.ind``, the
+    IID column of a ``.psam`` (a file without a header line is read as a ``.fam``).  The names are those the readers
+    match the sample lists against."""
+    import gzip
+    import struct
+
+    reader = reader_for(path)
+    if reader in (plink, eigenstrat, pgen):
+        with open(reader.fileset_prefix(path) + {plink: ".fam", eigenstrat: ".ind", pgen: ".psam"}[reader]) as f:
+            rows = [line.split() for line in f if line.split()]
+        if reader is eigenstrat:  # a line whose first word begins with # is a comment
+            return [row[0] for row in rows if not row[0].startswith("#")]
+        column = 1
+        if reader is pgen and rows and rows[0][0].startswith("#"):  # a header line: #IID ..., or #FID IID ...
+            column = 0 if rows[0][0] == "#IID" else 1
+            rows = [row for row in rows if not row[0].startswith("#")]
+        return [row[column] for row in rows]
+    with open(path, "rb") as f:
+        compressed = f.read(2) == b"\x1f\x8b"
+    if reader is bcf:
+        with gzip.open(path, "rb") as f:
+            magic, l_text = struct.unpack("<5sI", f.read(9))
+            text = f.read(l_text).split(b"\0", 1)[0].decode("utf-8", "replace")
+        return _chrom_line_samples(path, text.splitlines())
+    with (gzip.open(path, "rt") if compressed else open(path)) as f:
+        return _chrom_line_samples(path, f)
+
+
 def release_buffers(eng) -> None:
     for reader in READERS + FILE_READERS:
         reader.release_buffers(eng)

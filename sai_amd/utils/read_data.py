@@ -93,9 +93,17 @@ def read_dosage_data(
 
     ``src_file``: the samples of the ``src`` group are read from that file, those of the other groups from ``vcf_file``,
     each by its own reader with the same ancestral alleles; the blocks hold the sites both readers kept
-    (``sai_amd.site_join``), and the result carries ``"site_join"``, the join's summary."""
+    (``sai_amd.site_join``), and the result carries ``"site_join"``, the join's summary.  A list or tuple of 2 to 16 paths:
+    every sample of the ``src`` group comes from the one file that holds it, and the blocks hold the sites all readers kept
+    (``sai_amd.site_join_many``); a sequence of one path is that path."""
     if src_file is not None:
         from ..site_join import join_host_results, require_second_input
+        from ..site_join_many import is_many, read_host, source_files
+
+        src_file = source_files(src_file)
+        if is_many(src_file):
+            return read_host(vcf_file, src_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
+                             anc_allele_file, start, end, engine)  # fmt: skip
 
         require_second_input(src_file, anc_allele_file)
         panel = read_dosage_data(vcf_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, None, out_ind_file, anc_allele_file,
@@ -225,19 +233,26 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
     ``vcf_file``, each by its own reader with the same region and ancestral alleles; the positions are joined on the host
     (``site_join.join_host``) and every population of both inputs is tiled from the rows of the common sites by one
     launch that gathers while it re-tiles (``site_join_device.RowTiler``).  All blocks share one ``POS``, the common
-    positions, and the result carries ``"site_join"``, as ``read_dosage_data(..., src_file=)``'s does."""
+    positions, and the result carries ``"site_join"``, as ``read_dosage_data(..., src_file=)``'s does.  A list or tuple of 2 to
+    16 paths: as there, and a population whose samples lie in more than one file is tiled from all of them by one launch
+    (``site_join_parts.tile_parts``)."""
     import torch
 
     from .filesets import reader_for
 
     if src_file is not None:
         from ..site_join import require_second_input
+        from ..site_join_many import as_list, is_many, read_device, source_files
 
-        require_second_input(src_file, anc_allele_file)
+        src_file = source_files(src_file)
+        require_second_input(as_list(src_file)[0], anc_allele_file)
         if layout == "packed2":
             raise ValueError("a source file of its own is read in the int8 layout: `src_file` cannot be combined with layout 'packed2'.")
         if layout != "int8":
             raise ValueError("layout must be 'int8' or 'packed2'")
+        if is_many(src_file):
+            return read_device(eng, vcf_file, src_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
+                               anc_allele_file, start, end)  # fmt: skip
         return _read_joined_device(eng, vcf_file, src_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
                                    anc_allele_file, start, end)  # fmt: skip
     reader = reader_for(vcf_file)
@@ -268,11 +283,12 @@ def read_data_device(eng, vcf_file: str, chr_name: str, ploidy_config, ref_ind_f
 
 
 def _read_blocks_device(eng, reader, vcf_file, chr_name, ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file,
-                        anc_allele_file, start, end):
+                        anc_allele_file, start, end, samples_by_group=None):
     """What ``read_data_device`` has before it tiles: ``(samples_by_group, column, blocks, pos, n_matched)`` -- the
     samples of every group, (sample, ploidy) -> (pass, column of the pass's block), the int8 [record][sample] device
     block of every pass, the positions the reader kept and the records it met.  ``column`` is None (and nothing was
-    read) when no population with a ploidy entry names a sample."""
+    read) when no population with a ploidy entry names a sample.  ``samples_by_group``: the samples to read, in place of the
+    sample files (one source file's share of the ``src`` list)."""
     fileset = reader is not None
     if fileset:
         load_dosage_device = reader.load_dosage_device
@@ -280,7 +296,8 @@ def _read_blocks_device(eng, reader, vcf_file, chr_name, ploidy_config, ref_ind_
         from .device_vcf import load_dosage_device
 
     chr_name = str(chr_name)
-    samples_by_group = _parse_groups(ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file)
+    if samples_by_group is None:
+        samples_by_group = _parse_groups(ploidy_config, ref_ind_file, tgt_ind_file, src_ind_file, out_ind_file)
     # One streaming pass maps a VCF column to ONE output slot, so a sample that sits in populations of
     # different ploidy (the reference reads every population on its own, with its own ploidy:
     # utils.py:123-138) is tokenised in a further pass: passes[k] holds each sample at most once.
