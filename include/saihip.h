@@ -437,6 +437,11 @@ int sai_synth_gaps(sai_ctx* ctx, uint64_t seed, int32_t chrom, int64_t site0, in
 
 /* ---- ingest (host side, no GPU involved) ------------------------------------------------- */
 
+/* The largest allele index a GT sub-field may hold.  A larger one, counted towards the dosage or not, refuses
+ * the line as "dosage outside the int8 range" in the host reader (sai_vcf_load) and flags it in sai_tokenize_gt:
+ * far outside int8 already, and checked digit by digit, so that neither the value nor the sums can wrap. */
+#define SAI_GT_MAX_ALLELE 100000
+
 /* First and last POS of the first contiguous run of `chrom` records; -1/-1 when the chromosome
  * is absent.  Replaces the pysam scan of ChunkGenerator.__init__ (chunk_generator.py:64-73).
  * Plain, gzip and bgzip files are accepted. */

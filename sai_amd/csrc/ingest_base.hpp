@@ -241,7 +241,12 @@ void parse_lines(const char* begin, const char* end, const std::string& chrom, i
             ++g;
           } else if (ch >= '0' && ch <= '9') {
             a = 0;
-            do { a = a * 10 + (*g++ - '0'); } while (g < le && *g >= '0' && *g <= '9');
+            do {
+              a = a * 10 + (*g++ - '0');
+              // the tokenizer's guard (tokenize.hip::parse_field): checked at every digit, so `a` never wraps, and
+              // for an allele beyond the ploidy too
+              if (a > SAI_GT_MAX_ALLELE) { out.error = "dosage outside the int8 range at " + chrom + ":" + std::to_string(pos); return; }
+            } while (g < le && *g >= '0' && *g <= '9');
           } else if (ch == '|' || ch == '/' || ch == ':' || ch == '\t') {
             a = -1;  // empty allele
           } else {

@@ -6,7 +6,9 @@
 // step (one aligned 32-bit word per lane): four ballots mark the tabs, a prefix popcount gives every
 // byte its column number, and the lane that holds the first byte of a selected column parses that
 // field -- the same state machine as parse_lines() of the host reader, so both give the same bytes
-// (tests/test_ingest_device.py compares them on every awkward file of the host reader's tests).
+// (tests/test_ingest_device.py compares them on every awkward file of the host reader's tests;
+// tests/test_tokenize_device.py calls the kernel on hand-built lines: a field starting at every byte of
+// three steps, line ends around a step boundary, the rules one line each).
 
 #include "common.hpp"
 
@@ -46,7 +48,7 @@ __device__ __forceinline__ bool parse_field(const char* g, const char* le, int g
       a = 0;
       do {
         a = a * 10 + (*g++ - '0');
-        if (a > 100000) return false;  // far outside int8 already; keeps the product from wrapping
+        if (a > SAI_GT_MAX_ALLELE) return false;  // far outside int8 already; keeps the product from wrapping
       } while (g < le && *g >= '0' && *g <= '9');
     } else if (ch == '|' || ch == '/' || ch == ':' || ch == '\t') {
       a = -1;  // empty allele

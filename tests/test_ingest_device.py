@@ -87,13 +87,21 @@ def test_device_reader_edge_lines_and_errors(eng, tmp_path):
     assert np.array_equal(got[1].cpu().numpy(), want[1])
     for body, msg in (("1\t10\t.\tA\tT\t.\t.\t.\tGT\t0|1\t0|x\t0|0\n", "unparsable genotype"),
                       ("1\t10\t.\tA\tT\t.\t.\t.\tGT\t0|1\t0|1\n", "too few sample columns"),
-                      ("1\t10\t.\tA\tT\t.\t.\t.\tGT\t0|1\t99|99\t0|0\n", "int8")):  # fmt: skip
+                      ("1\t10\t.\tA\tT\t.\t.\t.\tGT\t0|1\t99|99\t0|0\n", "int8"),
+                      # an allele index above SAI_GT_MAX_ALLELE: beyond the ploidy, and with more digits than an int holds
+                      ("1\t10\t.\tA\tT\t.\t.\t.\tGT\t0|1\t0|1|100001\t0|0\n", "dosage outside the int8 range at 1:10"),
+                      ("1\t10\t.\tA\tT\t.\t.\t.\tGT\t0|1\t0|99999999999\t0|0\n", "dosage outside the int8 range at 1:10")):  # fmt: skip
         bad = tmp_path / "bad.vcf"
         bad.write_text(head + "1\t5\t.\tA\tT\t.\t.\t.\tGT\t0|0\t0|0\t0|0\n" + body)
         with pytest.raises(ValueError, match=msg):
             load_dosage(str(bad), "1", ["a", "b", "c"], [2, 2, 2])
         with pytest.raises(ValueError, match=msg):
             load_dosage_device(eng, str(bad), "1", ["a", "b", "c"], [2, 2, 2])
+        if "99999" in body or "100001" in body:  # the same bytes in a column that is not selected: both routes read past them
+            got = load_dosage_device(eng, str(bad), "1", ["c", "a"], [2, 2])
+            want = load_dosage(str(bad), "1", ["c", "a"], [2, 2])
+            assert got[0].tolist() == want[0].tolist() == [5, 10] and np.array_equal(got[1].cpu().numpy(), want[1])
+            assert want[1].tolist() == [[0, 0], [0, 1]]
     # a line longer than the staging buffer: the stream refuses, the caller sees a ValueError
     rng = np.random.default_rng(2)
     wide = tmp_path / "wide.vcf"

@@ -155,6 +155,19 @@ def test_native_errors(tmp_path, in_repo_root):
     weird.write_text("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\ta\n21\t5\t.\tA\tT\t.\t.\t.\tGT\t0|x\n")
     with pytest.raises(ValueError, match="unparsable genotype at 21:5"):
         load_dosage(str(weird), "21", ["a"], [2])
+    # an allele index above SAI_GT_MAX_ALLELE is outside int8 wherever it stands in a GT that is read -- beyond the
+    # ploidy too, and before eleven digits can wrap -- and nothing at all in a column that is not selected
+    head = "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\ta\tb\tc\n"
+    for call in ("0|1|100001", "0|99999999999"):
+        big = tmp_path / "big.vcf"
+        big.write_text(head + f"21\t5\t.\tA\tT\t.\t.\t.\tGT\t0|0\t1|1\t0|1\n21\t7\t.\tA\tT\t.\t.\t.\tGT\t0|1\t{call}\t1|1\n")
+        for ploidies in ([2, 2, 2], [1, 3, 4]):
+            with pytest.raises(ValueError, match="dosage outside the int8 range at 21:7"):
+                load_dosage(str(big), "21", ["a", "b", "c"], ploidies)
+        pos, dos, _, _ = load_dosage(str(big), "21", ["c", "a"], [2, 2])
+        assert pos.tolist() == [5, 7] and dos.tolist() == [[1, 0], [2, 1]]
+    big.write_text(head + "21\t7\t.\tA\tT\t.\t.\t.\tGT\t0|1\t0|1|100000\t1|1\n")  # the largest index, beyond the ploidy: kept
+    assert load_dosage(str(big), "21", ["a", "b", "c"], [2, 2, 2])[1].tolist() == [[1, 1, 2]]
     pc = PloidyConfig({"ref": {"ref1": 2}, "tgt": {"tgt1": 2, "tgt2": 2}, "src": {"src1": 2, "src2": 2}})
     for engine in ("native", "python"):
         with pytest.raises(ValueError, match="No ancestral allele is found for chromosome 21 in the region 16000-20000"):
