@@ -31,6 +31,7 @@ HOST_UNITS = [
     "plink/bed_encode_host.cpp",
     "plink/vcf_sites.cpp",
     "eigenstrat/eigenstrat_index.cpp",
+    "eigenstrat/geno_encode_host.cpp",
     "pgen/pgen_index.cpp",
     "pgen/pgen_pack2_host.cpp",
     "pgen/pgen_encode_host.cpp",
@@ -60,6 +61,7 @@ UNITS = [
     "plink/bed_encode.hip",
     "eigenstrat/geno_decode.hip",
     "eigenstrat/geno_transpose.hip",
+    "eigenstrat/geno_encode.hip",
     "pgen/pgen_decode.hip",
     "pgen/pgen_pack2.hip",
     "pgen/pgen_encode.hip",
@@ -222,10 +224,11 @@ def build(force: bool = False, sanitize: bool = False) -> None:
 
     for module in family_modules():  # every symbol of include/saihip.h and of each include/saihip_X.h resolves
         module.load()
-    from sai_amd.utils import bed_writer, pgen_writer  # ... and the converters', declared in csrc/plink/bed_export.hpp and csrc/pgen/pgen_export.hpp
+    from sai_amd.utils import bed_writer, geno_writer, pgen_writer  # ... and the converters', declared in csrc/plink/bed_export.hpp, csrc/pgen/pgen_export.hpp and csrc/eigenstrat/geno_export.hpp
 
     bed_writer.load()
     pgen_writer.load()
+    geno_writer.load()
     from sai_amd import site_join_device  # ... and the gathering re-tile's, declared by its own unit (csrc/join/tile_rows.hip)
 
     site_join_device.load()

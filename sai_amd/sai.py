@@ -367,23 +367,37 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
 
 
 def convert(vcf_file: str, chr_name: str, out_prefix: str = None, ploidy: int = 2, haploid_samples=None, samples=None, start: int = None,
-            end: int = None, append: bool = False, skip_multiallelic: bool = False, out_pfile: str = None) -> dict:  # fmt: skip
-    """Write one chromosome of a VCF (plain, gzip or bgzip) as the PLINK 1 fileset ``out_prefix`` (.bed / .bim / .fam)
-    or as the PLINK 2 fileset ``out_pfile`` (.pgen / .pvar / .psam: about a third of the .bed's bytes), encoded on the
+            end: int = None, append: bool = False, skip_multiallelic: bool = False, out_pfile: str = None, out_eigenstrat: str = None,
+            geno_format: str = "packed", labels=None) -> dict:  # fmt: skip
+    """Write one chromosome of a VCF (plain, gzip or bgzip) as the PLINK 1 fileset ``out_prefix`` (.bed / .bim / .fam),
+    as the PLINK 2 fileset ``out_pfile`` (.pgen / .pvar / .psam: about a third of the .bed's bytes) or as the EIGENSOFT
+    fileset ``out_eigenstrat`` (.geno / .snp / .ind, what ADMIXTOOLS reads; ``geno_format`` = "packed", the default, or
+    "transposed"; ``labels`` = sample name -> population label of its ``.ind`` line), encoded on the
     GPU: not a command of the reference.  Reading the fileset at the ploidies it was written with gives the block the
     VCF reader gives, byte for byte, so ``score`` on it writes the same files -- from either layout.  The arguments,
-    the summary it returns and the refusals: ``utils.bed_writer.convert`` and ``utils.pgen_writer.convert``.  The
+    the summary it returns and the refusals: ``utils.bed_writer.convert``, ``utils.pgen_writer.convert`` and
+    ``utils.geno_writer.convert``.  The
     ``.pgen`` rules were written from memory of the specification: the output is read back by this project's readers
-    and equals its test writer's, and has not been opened with plink2."""
-    if (out_prefix is None) == (out_pfile is None):
-        raise ValueError("convert writes one fileset: name either out_prefix (PLINK 1) or out_pfile (PLINK 2)")
+    and equals its test writer's, and has not been opened with plink2.  The two hashes in the header record of a
+    ``.geno`` were written from memory of EIGENSOFT's ``hasharr`` and are unverified; ``hashcheck: NO`` in a
+    ``convertf`` / ADMIXTOOLS parameter file is the way around a mismatch."""
+    given = [name for name, value in (("out_prefix", out_prefix), ("out_pfile", out_pfile), ("out_eigenstrat", out_eigenstrat)) if value is not None]
+    if len(given) != 1:
+        raise ValueError("convert writes one fileset: name either out_prefix (PLINK 1) or out_pfile (PLINK 2) or out_eigenstrat (EIGENSOFT)"
+                         + (f", not {' and '.join(given)}" if given else ""))  # fmt: skip
+    if out_eigenstrat is None and (geno_format != "packed" or labels is not None):
+        raise ValueError("geno_format and labels go with out_eigenstrat: the PLINK filesets have one form and no population column")
+    common = dict(ploidy=ploidy, haploid_samples=haploid_samples, samples=samples, start=start, end=end, append=append, skip_multiallelic=skip_multiallelic)
+    if out_eigenstrat is not None:
+        from .utils.geno_writer import convert as write_geno
+
+        return write_geno(vcf_file, chr_name, out_eigenstrat, geno_format=geno_format, labels=labels, **common)
     if out_pfile is not None:
         from .utils.pgen_writer import convert as write_fileset
     else:
         from .utils.bed_writer import convert as write_fileset
 
-    return write_fileset(vcf_file, chr_name, out_prefix if out_pfile is None else out_pfile, ploidy=ploidy, haploid_samples=haploid_samples,
-                         samples=samples, start=start, end=end, append=append, skip_multiallelic=skip_multiallelic)  # fmt: skip
+    return write_fileset(vcf_file, chr_name, out_prefix if out_pfile is None else out_pfile, **common)
 
 
 def outlier(score_file: str, output_prefix: str, quantile: float) -> None:

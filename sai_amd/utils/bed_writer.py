@@ -266,19 +266,12 @@ def _write_rows_host(dos, uniform, per_slot, target, ms, n_threads):
     return status, written
 
 
-def _write_rows_device(eng, dos, uniform, per_slot, target, ms):
-    """GPU route: batch k is encoded and copied into one of two pinned buffers on a side stream while a thread writes
-    batch k - 1 out of the other.  -> (status, bytes written)"""
+def _stream_batches(eng, f, cap, sizes, launch, ms, thread_name):
+    """The device writers' loop: ``launch(i, out_ptr, side)`` encodes batch i (``sizes[i]`` bytes, at most ``cap``) into
+    the device buffer at ``out_ptr`` on the side stream; the bytes are copied into one of two pinned buffers there while
+    a thread writes batch i - 1 to ``f`` out of the other.  -> bytes written"""
     import torch
 
-    lib = eng.lib
-    load()
-    n_rows, n_slots = dos.shape
-    row_bytes = (n_slots + 3) // 4
-    step = _batch_rows(row_bytes)
-    cap = min(step, n_rows) * row_bytes
-    status = torch.empty((n_rows,), dtype=torch.int32, device=eng.device)
-    ploidy_dev = None if per_slot is None else torch.from_numpy(per_slot).to(eng.device)
     rows_dev = [torch.empty((cap,), dtype=torch.uint8, device=eng.device) for _ in range(2)]
     pinned = [eng.pinned_acquire(cap) for _ in range(2)]
     side = torch.cuda.Stream(device=eng.device)
@@ -287,7 +280,7 @@ def _write_rows_device(eng, dos, uniform, per_slot, target, ms):
     jobs, failure, events = queue.Queue(), [], []
     written = 0
 
-    def writer(f):
+    def writer():
         while True:
             job = jobs.get()
             if job is None:
@@ -305,32 +298,29 @@ def _write_rows_device(eng, dos, uniform, per_slot, target, ms):
                 free[b].release()
 
     try:
-        with target.open_bed() as f:
-            thread = threading.Thread(target=writer, args=(f,), name="sai-bed-writer")
-            thread.start()
-            try:
-                for i, k0 in enumerate(range(0, n_rows, step)):
-                    k1, b = min(k0 + step, n_rows), i & 1
-                    nbytes = (k1 - k0) * row_bytes
-                    free[b].acquire()  # the writer has left this pinned buffer
-                    if failure:
-                        free[b].release()
-                        break
-                    marks = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-                    with torch.cuda.stream(side):
-                        marks[0].record(side)
-                        _ffi.check(lib.sai_bed_encode(eng.ctx, C.c_void_p(dos.data_ptr() + k0 * n_slots), k1 - k0, n_slots, eng._ptr(ploidy_dev), uniform,
-                                                      C.c_void_p(rows_dev[b].data_ptr()), C.c_void_p(status.data_ptr() + 4 * k0), C.c_void_p(side.cuda_stream)))  # fmt: skip
-                        marks[1].record(side)
-                        pinned[b][:nbytes].copy_(rows_dev[b][:nbytes], non_blocking=True)
-                        marks[2].record(side)
-                    events.append(marks)
-                    jobs.put((b, nbytes, marks[2]))
-                    written += nbytes
-            finally:
-                jobs.put(None)
-                thread.join()
-                side.synchronize()
+        thread = threading.Thread(target=writer, name=thread_name)
+        thread.start()
+        try:
+            for i, nbytes in enumerate(sizes):
+                b = i & 1
+                free[b].acquire()  # the writer has left this pinned buffer
+                if failure:
+                    free[b].release()
+                    break
+                marks = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                with torch.cuda.stream(side):
+                    marks[0].record(side)
+                    launch(i, C.c_void_p(rows_dev[b].data_ptr()), side)
+                    marks[1].record(side)
+                    pinned[b][:nbytes].copy_(rows_dev[b][:nbytes], non_blocking=True)
+                    marks[2].record(side)
+                events.append(marks)
+                jobs.put((b, nbytes, marks[2]))
+                written += nbytes
+        finally:
+            jobs.put(None)
+            thread.join()
+            side.synchronize()
         if failure:
             raise failure[0]
     finally:
@@ -340,10 +330,36 @@ def _write_rows_device(eng, dos, uniform, per_slot, target, ms):
         ms["encode"] += start.elapsed_time(encoded)
         ms["d2h"] += encoded.elapsed_time(copied)
     torch.cuda.current_stream(eng.device).wait_stream(side)
+    return written
+
+
+def _write_rows_device(eng, dos, uniform, per_slot, target, ms):
+    """GPU route: batch k is encoded and copied into one of two pinned buffers on a side stream while a thread writes
+    batch k - 1 out of the other (``_stream_batches``).  -> (status, bytes written)"""
+    import torch
+
+    lib = eng.lib
+    load()
+    n_rows, n_slots = dos.shape
+    row_bytes = (n_slots + 3) // 4
+    step = _batch_rows(row_bytes)
+    status = torch.empty((n_rows,), dtype=torch.int32, device=eng.device)
+    ploidy_dev = None if per_slot is None else torch.from_numpy(per_slot).to(eng.device)
+    starts = list(range(0, n_rows, step))
+
+    def launch(i, out_ptr, side):
+        k0 = starts[i]
+        k1 = min(k0 + step, n_rows)
+        _ffi.check(lib.sai_bed_encode(eng.ctx, C.c_void_p(dos.data_ptr() + k0 * n_slots), k1 - k0, n_slots, eng._ptr(ploidy_dev), uniform,
+                                      out_ptr, C.c_void_p(status.data_ptr() + 4 * k0), C.c_void_p(side.cuda_stream)))  # fmt: skip
+
+    with target.open_bed() as f:
+        written = _stream_batches(eng, f, min(step, n_rows) * row_bytes, [(min(k0 + step, n_rows) - k0) * row_bytes for k0 in starts], launch, ms,
+                                  "sai-bed-writer")  # fmt: skip
     return status.cpu().numpy(), written
 
 
-# the words a refusal names the output by: the shared steps serve this module and utils/pgen_writer.py
+# the words a refusal names the output by: the shared steps serve this module, utils/pgen_writer.py and utils/geno_writer.py
 _BED_WORDS = dict(fileset="PLINK 1 fileset", sample_file=".fam", row=".bed row")
 
 
@@ -354,7 +370,8 @@ def _samples_to_write(vcf_file, ploidy, samples, haploid_samples, words):
     if kind is not None:
         raise ValueError(f"{vcf_file} is {kind}, already a binary format: `sai score` reads it as it is; `sai convert` takes VCF text (plain, gzip or bgzip)")
     if ploidy not in (1, 2):
-        raise ValueError(f"ploidy {ploidy}: a {words['fileset']} holds haploid and diploid calls only (--ploidy 1 or 2)")
+        article = "an" if words["fileset"][0] in "AEIOU" else "a"
+        raise ValueError(f"ploidy {ploidy}: {article} {words['fileset']} holds haploid and diploid calls only (--ploidy 1 or 2)")
     if not os.path.isfile(vcf_file):
         raise ValueError(f"{vcf_file} is not found")
     in_file = header_samples(vcf_file)
