@@ -39,6 +39,7 @@ HOST_UNITS = [
     "bcf/bcf_feed.cpp",
     "bcf/csi_index.cpp",
     "packed_stats/packed2_freqs_host.cpp",
+    "dd_table/dd_table_host.cpp",
     "join/site_join_host.cpp",
     "join/site_join_many_host.cpp",
 ]
@@ -68,6 +69,7 @@ UNITS = [
     "bcf/bcf_decode.hip",
     "bcf/bcf_walk.hip",
     "packed_stats/packed2_freqs.hip",
+    "dd_table/dd_table.hip",
     "join/tile_parts.hip",
     "join/tile_rows.hip",
     *HOST_UNITS,
@@ -236,3 +238,6 @@ def build(force: bool = False, sanitize: bool = False) -> None:
 
     site_join_many.load()
     site_join_parts.load()
+    from sai_amd import dd_table  # ... and DD's tables of per-site terms, declared by their own units (csrc/dd_table/)
+
+    dd_table.load()

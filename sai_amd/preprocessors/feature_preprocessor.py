@@ -330,6 +330,7 @@ class FeaturePreprocessor(DataPreprocessor):
         win_arrays = wg.__dict__.setdefault("_win_arrays", {})  # the grid as int64 [n][2], once per generator (0.7 ms for 10^4 tuples)
         scorers = wg.__dict__.setdefault("_scorers", {})
         group_data = {"ref": wg.ref_data, "tgt": wg.tgt_data, "src": wg.src_data, "outgroup": wg.out_data}
+        dd_pair = None  # DD's tables of one (ref, tgt) pair of blocks, shared by the source combinations of this call (dd_table.py)
         for ref_pop, tgt_pop, src_comb, out_pop in combos:
             al = wg.aligned(ref_pop, tgt_pop, src_comb, out_pop)
             pos = al.pos_rows
@@ -462,16 +463,18 @@ class FeaturePreprocessor(DataPreprocessor):
                                               lo, hi).cpu().numpy())  # fmt: skip
                     row += n
                 cb.dd = np.stack(cols, axis=1)
-            elif want_dd:  # more source individuals than ride along: two streaming passes per pair of them
+            elif want_dd:  # more source individuals than ride along
+                from .. import dd_table
+
                 ref_t, tgt_t = tiled[("ref", ref_pop)], tiled[("tgt", tgt_pop)]
-                cb.dd = np.stack(
-                    [
-                        eng.window_dd(eng.site_absdiff(ref_t, tiled[("src", s)]), ref_t.n_ind,
-                                      eng.site_absdiff(tgt_t, tiled[("src", s)]), tgt_t.n_ind, lo, hi).cpu().numpy()
-                        for s in src_comb
-                    ],
-                    axis=1,
-                )  # fmt: skip
+                srcs = [tiled[("src", s)] for s in src_comb]
+                if len(src_ploidies) >= len(src_comb) and dd_table.table_route_admitted(src_ploidies[: len(src_comb)], sum(s.n_ind for s in srcs)):
+                    # ref and tgt are read once, whatever the number of source individuals: a table of DD's term for every
+                    # value a source byte can hold, kept for the next combination of the same pair (dd_table.py)
+                    dd_pair = dd_pair or dd_table.TablePair()
+                    cb.dd = dd_table.combination_dd(eng, dd_pair, ref_t, tgt_t, srcs, lo, hi)
+                else:  # sources of ploidy above 2, SAI_AMD_DD_TABLE=0: two streaming passes per pair of source individuals
+                    cb.dd = np.stack([dd_table.old_route_dd(eng, ref_t, tgt_t, s, lo, hi).cpu().numpy() for s in srcs], axis=1)
             if sink is not None:
                 sink(cb)
         return batch
