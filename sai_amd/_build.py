@@ -35,6 +35,7 @@ HOST_UNITS = [
     "pgen/pgen_index.cpp",
     "pgen/pgen_pack2_host.cpp",
     "pgen/pgen_encode_host.cpp",
+    "pgen/pgen_encode_ld_host.cpp",
     "bcf/bcf_index.cpp",
     "bcf/bcf_feed.cpp",
     "bcf/csi_index.cpp",
@@ -66,6 +67,7 @@ UNITS = [
     "pgen/pgen_decode.hip",
     "pgen/pgen_pack2.hip",
     "pgen/pgen_encode.hip",
+    "pgen/pgen_encode_ld.hip",
     "bcf/bcf_decode.hip",
     "bcf/bcf_walk.hip",
     "packed_stats/packed2_freqs.hip",
@@ -230,6 +232,7 @@ def build(force: bool = False, sanitize: bool = False) -> None:
 
     bed_writer.load()
     pgen_writer.load()
+    pgen_writer.load_ld()  # ... with the LD-compressing encoder beside it, declared in csrc/pgen/pgen_export_ld.hpp
     geno_writer.load()
     from sai_amd import site_join_device  # ... and the gathering re-tile's, declared by its own unit (csrc/join/tile_rows.hip)
 

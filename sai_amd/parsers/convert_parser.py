@@ -16,6 +16,11 @@ GENO_NOTE = ("The two hashes in the header record of a .geno follow EIGENSOFT's 
              "because no EIGENSOFT program was at hand, and this project's reader ignores them. If convertf or an ADMIXTOOLS program reports "
              "a hash mismatch, put `hashcheck: NO` into its parameter file. EIGENSOFT programs want single-letter alleles; the alleles are "
              "written as the VCF spells them.")  # fmt: skip
+LD_NOTE = ("Neighbouring variants in linkage disequilibrium are near copies of each other, and --ld-compress lets every row but the first of each "
+           "16 be written as the list of its differences from an earlier row of its 16 (record types 2 and 3), where that is smaller: a "
+           "synthetic panel of near-copied rows came out at less than half the bytes, rows drawn independently at the same bytes; the gain "
+           "on a real panel is unmeasured. The fileset promises the same block. Reading it is slower, because the base row of every such "
+           "record is expanded first: `sai score` from that panel, warm, took 11.0 ms against 8.8 ms. " + PGEN_NOTE)  # fmt: skip
 
 
 def resolve_output(args: argparse.Namespace) -> None:
@@ -23,6 +28,8 @@ def resolve_output(args: argparse.Namespace) -> None:
     argparse's own words (a mutually exclusive group); the three-way rule is decided here and reported the same way, as
     a usage error with status 2, before anything is read or written."""
     error = args.convert_parser.error
+    if args.ld_compress and args.out_pfile is None:
+        error("--ld-compress goes with --out-pfile: only a .pgen holds records that list their differences from an earlier record")
     if args.out_eigenstrat is None:
         if args.out_bfile is None and args.out_pfile is None:
             error("one of the arguments --out-bfile --out-pfile is required, or --out-eigenstrat")
@@ -59,6 +66,7 @@ def _run_convert(args: argparse.Namespace) -> None:
             end=args.end,
             append=args.append,
             skip_multiallelic=args.skip_multiallelic,
+            **({"ld_compress": True} if args.ld_compress else {}),
             **extra,
         )
     except ValueError as exc:
@@ -85,6 +93,7 @@ def add_convert_parser(subparsers) -> None:
     out.add_argument("--out-pfile", dest="out_pfile", type=str, default=None, metavar="PREFIX",
                      help="Prefix of the PLINK 2 fileset to write. An existing PREFIX.pgen is refused, and so is --append: the record table "
                      "of a .pgen sits at the front of the file. Write one fileset per chromosome, or use --out-bfile.")  # fmt: skip
+    parser.add_argument("--ld-compress", dest="ld_compress", action="store_true", help="With --out-pfile only. " + LD_NOTE)
     parser.add_argument("--out-eigenstrat", dest="out_eigenstrat", type=str, default=None, metavar="PREFIX",
                         help="Prefix of the EIGENSOFT fileset to write: PREFIX.geno, PREFIX.snp (`ID CHROM 0.0 POS REF ALT`; an ID of `.` is "
                         "written CHROM:POS) and PREFIX.ind (`NAME U LABEL`; LABEL, the population to ADMIXTOOLS, is the second word of the "

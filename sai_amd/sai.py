@@ -368,7 +368,7 @@ def score(vcf_file: str, chr_name: str, win_len: int, win_step: int, anc_allele_
 
 def convert(vcf_file: str, chr_name: str, out_prefix: str = None, ploidy: int = 2, haploid_samples=None, samples=None, start: int = None,
             end: int = None, append: bool = False, skip_multiallelic: bool = False, out_pfile: str = None, out_eigenstrat: str = None,
-            geno_format: str = "packed", labels=None) -> dict:  # fmt: skip
+            geno_format: str = "packed", labels=None, ld_compress: bool = False) -> dict:  # fmt: skip
     """Write one chromosome of a VCF (plain, gzip or bgzip) as the PLINK 1 fileset ``out_prefix`` (.bed / .bim / .fam),
     as the PLINK 2 fileset ``out_pfile`` (.pgen / .pvar / .psam: about a third of the .bed's bytes) or as the EIGENSOFT
     fileset ``out_eigenstrat`` (.geno / .snp / .ind, what ADMIXTOOLS reads; ``geno_format`` = "packed", the default, or
@@ -376,7 +376,9 @@ def convert(vcf_file: str, chr_name: str, out_prefix: str = None, ploidy: int = 
     GPU: not a command of the reference.  Reading the fileset at the ploidies it was written with gives the block the
     VCF reader gives, byte for byte, so ``score`` on it writes the same files -- from either layout.  The arguments,
     the summary it returns and the refusals: ``utils.bed_writer.convert``, ``utils.pgen_writer.convert`` and
-    ``utils.geno_writer.convert``.  The
+    ``utils.geno_writer.convert``.  ``ld_compress``, with ``out_pfile`` only, also writes rows as their differences
+    from an earlier row (record types 2 and 3): a smaller file of a panel whose neighbouring variants resemble each other,
+    the same block when it is read.  The
     ``.pgen`` rules were written from memory of the specification: the output is read back by this project's readers
     and equals its test writer's, and has not been opened with plink2.  The two hashes in the header record of a
     ``.geno`` were written from memory of EIGENSOFT's ``hasharr`` and are unverified; ``hashcheck: NO`` in a
@@ -387,6 +389,8 @@ def convert(vcf_file: str, chr_name: str, out_prefix: str = None, ploidy: int = 
                          + (f", not {' and '.join(given)}" if given else ""))  # fmt: skip
     if out_eigenstrat is None and (geno_format != "packed" or labels is not None):
         raise ValueError("geno_format and labels go with out_eigenstrat: the PLINK filesets have one form and no population column")
+    if ld_compress and out_pfile is None:
+        raise ValueError("ld_compress goes with out_pfile: only a .pgen holds records that list their differences from an earlier record")
     common = dict(ploidy=ploidy, haploid_samples=haploid_samples, samples=samples, start=start, end=end, append=append, skip_multiallelic=skip_multiallelic)
     if out_eigenstrat is not None:
         from .utils.geno_writer import convert as write_geno
@@ -394,6 +398,9 @@ def convert(vcf_file: str, chr_name: str, out_prefix: str = None, ploidy: int = 
         return write_geno(vcf_file, chr_name, out_eigenstrat, geno_format=geno_format, labels=labels, **common)
     if out_pfile is not None:
         from .utils.pgen_writer import convert as write_fileset
+
+        if ld_compress:
+            common["ld_compress"] = True
     else:
         from .utils.bed_writer import convert as write_fileset
 

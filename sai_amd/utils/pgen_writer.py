@@ -14,8 +14,15 @@ block the VCF reader gives for the same samples, byte for byte.  The format rule
 specification; the output is read back by this project's readers and equals its test writer's, and has not been opened
 with plink2.  The table, the size rules and the refusals are in DESIGN_INGEST.md ("PLINK 2 filesets written from a VCF").
 
-The entry points are internal to the package: their declarations are in sai_amd/csrc/pgen/pgen_export.hpp, not
-under include/, and this module -- their only caller -- binds them, with a version number of their own.
+With ``ld_compress`` every row but the first of each 16 may also be written as its differences from an earlier row of
+its 16 (record types 2 and 3: ``sai_pgen_encode_ld``, sai_amd/csrc/pgen/pgen_encode_ld.hip; the rule is in
+sai_amd/csrc/pgen/pgen_export_ld.hpp and DESIGN_INGEST.md, "LD-compressed records").  Neighbouring variants in linkage
+disequilibrium are near copies of each other, so such a file is smaller; it promises the same block.  Off by default:
+without it nothing here differs from what it was.
+
+The entry points are internal to the package: their declarations are in sai_amd/csrc/pgen/pgen_export.hpp and
+pgen_export_ld.hpp, not under include/, and this module -- their only caller -- binds them, with version numbers of
+their own.
 """
 
 from __future__ import annotations
@@ -54,6 +61,20 @@ HOST_SYMBOLS = ("sai_pgen_export_abi_version", "sai_pgen_encode_host", "sai_pgen
 load, load_host = extension("pgen export", "sai_amd/csrc/pgen/pgen_export.hpp", "sai_pgen_export_abi_version", SAI_PGEN_EXPORT_ABI_VERSION,
                             SIGNATURES, HOST_SYMBOLS, built_from="pgen")  # fmt: skip
 
+# the LD-compressing encoder: a group of its own, so that the table above stays what pgen_export.hpp declares
+SAI_PGEN_EXPORT_LD_VERSION = 1
+LD_SEGMENT = 16  # rows of a segment: the first is an anchor, the others may list their differences from an earlier one
+LD_SIGNATURES = {
+    "sai_pgen_export_ld_version": (C.c_int, []),
+    "sai_pgen_ld_segment": (C.c_int, []),
+    "sai_pgen_encode_ld_host": SIGNATURES["sai_pgen_encode_host"],
+    "sai_pgen_encode_ld": SIGNATURES["sai_pgen_encode"],
+}
+LD_HOST_SYMBOLS = ("sai_pgen_export_ld_version", "sai_pgen_ld_segment", "sai_pgen_encode_ld_host")
+
+load_ld, load_ld_host = extension("pgen LD export", "sai_amd/csrc/pgen/pgen_export_ld.hpp", "sai_pgen_export_ld_version", SAI_PGEN_EXPORT_LD_VERSION,
+                                  LD_SIGNATURES, LD_HOST_SYMBOLS, built_from="pgen")  # fmt: skip
+
 _WORDS = dict(fileset="PLINK 2 fileset", sample_file=".psam", row=".pgen record")
 _ptr = bed_writer._ptr
 
@@ -90,18 +111,30 @@ def assemble_header(n_samples: int, vrtypes: np.ndarray, lengths: np.ndarray) ->
     return head
 
 
-def encode_host(dosage: np.ndarray, ploidies, n_threads: Optional[int] = None):
-    """(records uint8 [total], vrtype uint8 [n], length uint32 [n], status int32 [n]) of an int8 [n][slots] block:
-    ``sai_pgen_encode_host``.  ``ploidies`` = 1, 2 or one value per slot."""
+def _host_encoder(ld_compress: bool):
+    """``sai_pgen_encode_host``, or with ``ld_compress`` ``sai_pgen_encode_ld_host``, and the library that holds it."""
+    if ld_compress:
+        lib = load_ld_host()
+        if lib.sai_pgen_ld_segment() != LD_SEGMENT:
+            raise RuntimeError(f"libsaihip: LD segments of {lib.sai_pgen_ld_segment()} rows, and this module expects {LD_SEGMENT}")
+        return lib, lib.sai_pgen_encode_ld_host
     lib = load_host()
+    return lib, lib.sai_pgen_encode_host
+
+
+def encode_host(dosage: np.ndarray, ploidies, n_threads: Optional[int] = None, ld_compress: bool = False):
+    """(records uint8 [total], vrtype uint8 [n], length uint32 [n], status int32 [n]) of an int8 [n][slots] block:
+    ``sai_pgen_encode_host``, with ``ld_compress`` ``sai_pgen_encode_ld_host``.  ``ploidies`` = 1, 2 or one value per
+    slot."""
+    lib, encode = _host_encoder(ld_compress)
     dosage = np.ascontiguousarray(dosage, dtype=np.int8)
     n_rows, n_slots = dosage.shape
     uniform, per_slot = bed_writer._ploidy_arguments(ploidies)
     out = np.empty(n_rows * ((n_slots + 3) // 4), dtype=np.uint8)
     vrtype, length, status = np.zeros(n_rows, dtype=np.uint8), np.zeros(n_rows, dtype=np.uint32), np.zeros(n_rows, dtype=np.int32)
     total = _i64()
-    check_io(lib, lib.sai_pgen_encode_host(_ptr(dosage), n_rows, n_slots, _ptr(per_slot), uniform, _ptr(out), out.size, _ptr(vrtype), _ptr(length),
-                                           _ptr(status), C.byref(total), n_threads or default_threads()))  # fmt: skip
+    check_io(lib, encode(_ptr(dosage), n_rows, n_slots, _ptr(per_slot), uniform, _ptr(out), out.size, _ptr(vrtype), _ptr(length), _ptr(status),
+                         C.byref(total), n_threads or default_threads()))  # fmt: skip
     return out[: total.value], vrtype, length, status
 
 
@@ -145,9 +178,10 @@ def pvar_text(bim: bytes) -> bytes:
     return out.raw[: n.value]
 
 
-def _write_records_host(dos, uniform, per_slot, f, ms, n_threads):
-    """Host route: ``sai_pgen_encode_host`` batch by batch, written as it comes.  -> (vrtype, length, status)"""
-    lib = load_host()
+def _write_records_host(dos, uniform, per_slot, f, ms, n_threads, ld_compress=False):
+    """Host route: ``sai_pgen_encode_host`` (``sai_pgen_encode_ld_host``) batch by batch, written as it comes.  A batch
+    is a multiple of 16 rows, so the LD segments of a file do not depend on it.  -> (vrtype, length, status)"""
+    lib, encode = _host_encoder(ld_compress)
     n_rows, n_slots = dos.shape
     row_bytes = (n_slots + 3) // 4
     vrtype, length, status = np.zeros(n_rows, dtype=np.uint8), np.zeros(n_rows, dtype=np.uint32), np.zeros(n_rows, dtype=np.int32)
@@ -157,8 +191,8 @@ def _write_records_host(dos, uniform, per_slot, f, ms, n_threads):
     for k0 in range(0, n_rows, step):
         k1 = min(k0 + step, n_rows)
         t0 = time.perf_counter()
-        check_io(lib, lib.sai_pgen_encode_host(_ptr(dos[k0:k1]), k1 - k0, n_slots, _ptr(per_slot), uniform, _ptr(out), out.size, _ptr(vrtype[k0:k1]),
-                                               _ptr(length[k0:k1]), _ptr(status[k0:k1]), C.byref(total), n_threads))  # fmt: skip
+        check_io(lib, encode(_ptr(dos[k0:k1]), k1 - k0, n_slots, _ptr(per_slot), uniform, _ptr(out), out.size, _ptr(vrtype[k0:k1]), _ptr(length[k0:k1]),
+                             _ptr(status[k0:k1]), C.byref(total), n_threads))  # fmt: skip
         t1 = time.perf_counter()
         f.write(memoryview(out)[: total.value])
         ms["encode"] += (t1 - t0) * 1e3
@@ -166,15 +200,22 @@ def _write_records_host(dos, uniform, per_slot, f, ms, n_threads):
     return vrtype, length, status
 
 
-def _write_records_device(eng, dos, uniform, per_slot, f, ms):
+def _write_records_device(eng, dos, uniform, per_slot, f, ms, ld_compress=False):
     """GPU route, shaped like ``bed_writer._write_rows_device``: batch k is planned, scanned and written into a device
     buffer on a side stream, its total comes back (four bytes, the one wait of the batch), that many bytes are copied
     into one of two pinned buffers, and a thread writes batch k - 1 out of the other meanwhile.  The record types,
-    lengths and status values stay on the device until the last batch.  -> (vrtype, length, status)"""
+    lengths and status values stay on the device until the last batch.  ``ld_compress``: ``sai_pgen_encode_ld``.
+    -> (vrtype, length, status)"""
     import torch
 
     lib = eng.lib
     load()
+    encode = lib.sai_pgen_encode
+    if ld_compress:
+        load_ld()
+        if lib.sai_pgen_ld_segment() != LD_SEGMENT:
+            raise RuntimeError(f"libsaihip: LD segments of {lib.sai_pgen_ld_segment()} rows, and this module expects {LD_SEGMENT}")
+        encode = lib.sai_pgen_encode_ld
     n_rows, n_slots = dos.shape
     row_bytes = (n_slots + 3) // 4
     step = bed_writer._batch_rows(row_bytes)
@@ -222,9 +263,9 @@ def _write_records_device(eng, dos, uniform, per_slot, f, ms):
                 marks = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                 with torch.cuda.stream(side):
                     marks[0].record(side)
-                    _ffi.check(lib.sai_pgen_encode(eng.ctx, C.c_void_p(dos.data_ptr() + k0 * n_slots), k1 - k0, n_slots, eng._ptr(ploidy_dev), uniform,
-                                                   C.c_void_p(rec_dev[b].data_ptr()), C.c_void_p(vrtype.data_ptr() + k0), C.c_void_p(length.data_ptr() + 4 * k0),
-                                                   C.c_void_p(off_dev[b].data_ptr()), C.c_void_p(status.data_ptr() + 4 * k0), ENCODE_ALL, C.c_void_p(side.cuda_stream)))  # fmt: skip
+                    _ffi.check(encode(eng.ctx, C.c_void_p(dos.data_ptr() + k0 * n_slots), k1 - k0, n_slots, eng._ptr(ploidy_dev), uniform,
+                                      C.c_void_p(rec_dev[b].data_ptr()), C.c_void_p(vrtype.data_ptr() + k0), C.c_void_p(length.data_ptr() + 4 * k0),
+                                      C.c_void_p(off_dev[b].data_ptr()), C.c_void_p(status.data_ptr() + 4 * k0), ENCODE_ALL, C.c_void_p(side.cuda_stream)))  # fmt: skip
                     totals[b : b + 1].copy_(off_dev[b][k1 - k0 : k1 - k0 + 1], non_blocking=True)
                     marks[1].record(side)
                     marks[1].synchronize()
@@ -256,10 +297,11 @@ def _write_records_device(eng, dos, uniform, per_slot, f, ms):
 
 def convert(vcf_file: str, chr_name: str, out_prefix: str, ploidy: int = 2, haploid_samples: Optional[Sequence[str]] = None,
             samples: Optional[Sequence[str]] = None, start: Optional[int] = None, end: Optional[int] = None, append: bool = False,
-            skip_multiallelic: bool = False) -> dict:  # fmt: skip
+            skip_multiallelic: bool = False, ld_compress: bool = False) -> dict:  # fmt: skip
     """Write the records of ``chr_name`` (inside [start, end]) of a plain, gzip or bgzip VCF as the PLINK 2 fileset
     ``out_prefix``; see the module's text for what the fileset promises.  The arguments and the summary are those of
-    ``bed_writer.convert``; ``append`` is refused.  Every refusal is a ValueError that names the file and the cause and
+    ``bed_writer.convert``; ``append`` is refused.  ``ld_compress`` also writes record types 2 and 3 (the module's text),
+    and the summary then gains ``"record_types"``: record type -> how many records took it.  Every refusal is a ValueError that names the file and the cause and
     leaves nothing behind."""
     t_all = time.perf_counter()
     vcf_file, chr_name, out_prefix = os.fspath(vcf_file), str(chr_name), os.fspath(out_prefix)
@@ -280,10 +322,10 @@ def convert(vcf_file: str, chr_name: str, out_prefix: str, ploidy: int = 2, hapl
         try:
             with target.open_pgen(first) as f:
                 if calls.host:
-                    vrtype, length, status = _write_records_host(np.ascontiguousarray(dos), uniform, per_slot, f, ms, calls.n_threads)
+                    vrtype, length, status = _write_records_host(np.ascontiguousarray(dos), uniform, per_slot, f, ms, calls.n_threads, ld_compress)
                     dosage_at = lambda k, s: dos[k, s]  # noqa: E731
                 else:
-                    vrtype, length, status = _write_records_device(calls.eng, dos.contiguous(), uniform, per_slot, f, ms)
+                    vrtype, length, status = _write_records_device(calls.eng, dos.contiguous(), uniform, per_slot, f, ms, ld_compress)
                     dosage_at = lambda k, s: dos[k, s].item()  # noqa: E731
                 bed_writer._refuse_unfit(vcf_file, status, pos, names, ploidies, dosage_at, row=_WORDS["row"])
                 t0 = time.perf_counter()
@@ -297,5 +339,8 @@ def convert(vcf_file: str, chr_name: str, out_prefix: str, ploidy: int = 2, hapl
             target.rollback()
             raise
     ms["total"] = (time.perf_counter() - t_all) * 1e3
-    return {"rows_written": int(len(pos)), "rows_skipped": int(sites.n_rows - len(pos)), "samples": len(names), "bytes": int(written),
-            "ms": {k: round(v, 3) for k, v in ms.items()}}  # fmt: skip
+    summary = {"rows_written": int(len(pos)), "rows_skipped": int(sites.n_rows - len(pos)), "samples": len(names), "bytes": int(written),
+               "ms": {k: round(v, 3) for k, v in ms.items()}}  # fmt: skip
+    if ld_compress:
+        summary["record_types"] = {int(t): int(c) for t, c in zip(*np.unique(np.asarray(vrtype), return_counts=True))}
+    return summary
